@@ -14,11 +14,15 @@ fp32 (the reference's Keras float32: fp32 storage, tapes, gradients, optimizer s
 products on the exact-f32 MFMA or as the fp32-accurate three-term bf16 split -- each fp32 operand =
 h + m + l, six of the nine products, error <= 2x the exact kernel's vs fp64,
 tests/test_kernels_gpu.py test_lstmf_*split*; HFREP_FP32_EXACT=1 for exact-f32 everywhere) for the
-headline record, and a bf16 sub-record
+headline record, and (``--full``) a bf16 sub-record
 (bf16 MFMA with fp32 accumulation, fp32 master weights / optimizer) of the same config.
 
+A plain run times the fp32 headline only; ``--full`` adds the bf16 sub-record.  ``--dump-outputs DIR``
+writes what the last timed step left behind (parameters, optimizer slots, loss terms) as ``DIR/<name>.npy``.
+
 Usage:
-    python bench.py                         # 1 GPU, defaults
+    python bench.py                         # 1 GPU, defaults: the fp32 headline record
+    python bench.py --full                  # + the bf16 sub-record of the same config
     torchrun --nproc-per-node N bench.py --gpus N --steps K --warmup W
 """
 from __future__ import annotations
@@ -70,7 +74,25 @@ def _device_id(dev) -> str:
     return f"cuda:{dev.index} {p.name}" + (f" ({', '.join(str(t) for t in tags)})" if tags else "")
 
 
-def _measure(args, dtype, rank, world, pg, dev):
+def _dump_outputs(tr, out_dir):
+    """What a caller of the timed path holds after its last step, as float32 ``out_dir/<name>.npy``: both
+    models' flat parameter vectors, their optimizer slots (RMSprop: the running mean of the squared
+    gradients; the gradients themselves are zeroed by each update) and the loss terms of the step
+    (d_loss, d_real, d_fake, gp, g_loss).  About 2 MB at any batch size."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    rec = tr.losses()
+    arrays = {"losses": np.array([rec[k] for k in ("d_loss", "d_real", "d_fake", "gp", "g_loss")], dtype=np.float32)}
+    for name, model in (("generator", tr.generator), ("critic", tr.critic)):
+        arrays[f"{name}_params"] = model.flat.detach().float().cpu().numpy()
+        for i, slot in enumerate(tr.opt.slots.get(model.flat.data_ptr(), ())):
+            arrays[f"{name}_opt_slot{i}"] = slot.detach().float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _measure(args, dtype, rank, world, pg, dev, dump_dir=None):
     """Warm up, then time exactly args.steps training iterations at one compute dtype.
 
     The timed window is bracketed by a barrier and a device synchronisation on both sides; the
@@ -128,6 +150,8 @@ def _measure(args, dtype, rank, world, pg, dev):
         dist.all_reduce(w, op=dist.ReduceOp.SUM)
         exposed = [round(float(v), 3) for v in w.cpu()]
         gs.check_errors(blocking=True)
+    if dump_dir and rank == 0:
+        _dump_outputs(tr, dump_dir)
     if args.trace_out and rank == 0:
         from hfrep.utils.trace import profile_steps
 
@@ -178,9 +202,15 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=262144)
     ap.add_argument("--window", type=int, default=24)
     ap.add_argument("--features", type=int, default=32)
-    ap.add_argument("--dtype", default="both", choices=["both", "float32", "bfloat16"],
-                    help="both (default): the reference-precision fp32 record, plus a bf16 sub-record timed the "
-                         "same way right after it")
+    ap.add_argument("--dtype", default=None, choices=["both", "float32", "bfloat16"],
+                    help="float32 (default): the reference-precision fp32 record; both (the default under --full): "
+                         "plus a bf16 sub-record timed the same way right after it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the bf16 sub-record of the same config")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps: the headline run's parameters, optimizer slots and loss terms as "
+                         "float32 DIR/<name>.npy (same arguments -> same inputs, so two builds compare output "
+                         "for output)")
     ap.add_argument("--model", default="mtss_wgan_gp", choices=sorted(MODELS),
                     help="mtss_wgan_gp (default) is the BASELINE headline; gan / wgan_gp are BASELINE configs 3 / 4 "
                          "(GAN.py, WGAN_GP.py MLP models) measured the same way")
@@ -189,6 +219,8 @@ def main():
     ap.add_argument("--trace-out", default="", help="after the timed steps: torch.profiler Chrome trace of "
                     "--profile-steps (default 2) untimed steps with the trainer's phase ranges")
     args = ap.parse_args()
+    if args.dtype is None:
+        args.dtype = "both" if args.full else "float32"
 
     import torch
     import torch.distributed as dist
@@ -210,7 +242,7 @@ def main():
         dev = torch.device("cpu")
 
     primary = "float32" if args.dtype in ("both", "float32") else "bfloat16"
-    res = _measure(args, primary, rank, world, pg, dev)
+    res = _measure(args, primary, rank, world, pg, dev, dump_dir=args.dump_outputs or None)
     sub = _measure(args, "bfloat16", rank, world, pg, dev) if args.dtype == "both" else None
     T, F, B = args.window, args.features, args.batch_per_gpu
     if rank == 0:

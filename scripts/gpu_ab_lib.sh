@@ -18,7 +18,7 @@ for V in base "$@"; do
   done
   timeout -k 10 200 python -u scripts/bench_wgrad.py --dtype float32 --batch 262144 --iters 5 > $OUT/wgrad_$V.jsonl 2>&1 \
     || { tail -n 20 $OUT/wgrad_$V.jsonl; exit 1; }
-  timeout -k 10 300 python -u bench.py --steps 4 --warmup 2 > $OUT/bench_$V.json 2> $OUT/bench_$V.err \
+  timeout -k 10 300 python -u bench.py --full --steps 4 --warmup 2 > $OUT/bench_$V.json 2> $OUT/bench_$V.err \
     || { tail $OUT/bench_$V.err; exit 1; }
   echo "== $V"; grep -hv amdgpu.ids $OUT/lstm_${V}_K32.jsonl $OUT/lstm_${V}_K100.jsonl; grep -h '"kernel"' $OUT/wgrad_$V.jsonl; cat $OUT/bench_$V.json
 done

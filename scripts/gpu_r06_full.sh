@@ -11,9 +11,9 @@ if [ "$2" != "skip-tests" ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1 || { tail $OUT/smoke.txt; exit 1; }
   tail -n 1 $OUT/smoke.txt
 fi
-timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/bench.json')); print('headline', d['value'], d['ms_per_step'], d['bf16']['value'], d['bf16']['ms_per_step'])"
 for M in wgan_gp gan; do
-  timeout -k 10 300 python -u bench.py --model $M --steps 5 --warmup 2 > $OUT/bench_$M.json 2> $OUT/bench_$M.err || { tail $OUT/bench_$M.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --model $M --steps 5 --warmup 2 > $OUT/bench_$M.json 2> $OUT/bench_$M.err || { tail $OUT/bench_$M.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/bench_$M.json')); print('$M', d['value'], d['ms_per_step'], d['bf16']['value'], d['bf16']['ms_per_step'])"
 done

@@ -12,5 +12,5 @@ for M in wgan_gp gan; do
     || { tail $OUT/bench_$M.err; exit 1; }
   cut -c100-160 $OUT/bench_$M.json
 done
-timeout -k 10 400 python -u bench.py --steps 6 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --steps 6 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 cut -c1-400 $OUT/bench.json

@@ -1,8 +1,8 @@
 """Shared pytest setup.
 
 * ``gpu`` marker: tests that need a real MI355X (run with ``-m gpu`` on the GPU box).
-* ``data`` fixture: the reference dataset (cleaned_data + raw data/) if present; tests that
-  need it skip when it is absent (e.g. on the GPU box, where only the repo snapshot exists).
+* ``data_root`` / ``cleaned`` / ``daily`` fixtures: the reference dataset (cleaned_data + raw data/ +
+  the shipped generators) from tests/golden/reference, so every test runs from the repository alone.
 """
 import os
 import sys
@@ -21,33 +21,38 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "slow: long-running test")
 
 
-def _first_root_with(sub):
-    from hfrep.data.io import data_root as _dr
-
-    for r in (os.environ.get("HFREP_DATA_ROOT"), "/root/reference", _dr()):
-        if r and os.path.isdir(os.path.join(r, sub)):
-            return r
-    return None
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference")
 
 
 @pytest.fixture(scope="session")
-def data_root():
-    """A root with the RAW reference data (data/) and cleaned_data/."""
-    r = _first_root_with("data")
-    if r is None or not os.path.isdir(os.path.join(r, "cleaned_data")):
-        pytest.skip("reference dataset not available")
-    return r
+def data_root(tmp_path_factory):
+    """A root with the RAW reference data (data/), cleaned_data/ and the shipped generators (GAN/): the
+    files stored under tests/golden/reference in the reference layout, the CSV files (stored xz-packed)
+    unpacked under their own names.  Also the session's ``HFREP_DATA_ROOT``, so library calls that look
+    the dataset up themselves read the same files."""
+    import lzma
+
+    root = tmp_path_factory.mktemp("reference")
+    for d, _, files in os.walk(GOLDEN):
+        out = root / os.path.relpath(d, GOLDEN)
+        out.mkdir(exist_ok=True)
+        for f in files:
+            src = os.path.join(d, f)
+            if f.endswith(".xz"):
+                with lzma.open(src) as fh:
+                    (out / f[:-3]).write_bytes(fh.read())
+            else:
+                os.symlink(src, out / f)
+    os.environ["HFREP_DATA_ROOT"] = str(root)
+    return str(root)
 
 
 @pytest.fixture(scope="session")
-def cleaned():
-    """The cleaned panel only (cleaned_data/: also staged under assets/ for GPU runs)."""
-    r = _first_root_with("cleaned_data")
-    if r is None:
-        pytest.skip("cleaned reference data not available")
+def cleaned(data_root):
+    """The cleaned panel (cleaned_data/)."""
     from hfrep.data.io import load_cleaned
 
-    return load_cleaned(r)
+    return load_cleaned(data_root)
 
 
 @pytest.fixture
@@ -63,16 +68,8 @@ def cuda():
 
 
 @pytest.fixture(scope="session")
-def daily():
-    """The daily ETF excess-return matrix (staged CSV on GPU boxes, else built from the raw data)."""
-    r = _first_root_with("cleaned_data")
-    if r is None:
-        pytest.skip("reference dataset not available")
-    staged = os.path.exists(os.path.join(r, "cleaned_data", "factor_etf_daily.csv"))
-    if not staged and not os.path.isdir(os.path.join(r, "data")):
-        r = _first_root_with("data")
-        if r is None:
-            pytest.skip("daily ETF prices not available")
+def daily(data_root):
+    """The daily ETF excess-return matrix, built from the raw prices."""
     from hfrep.data.io import load_daily_etf
 
-    return load_daily_etf(r)[0]
+    return load_daily_etf(data_root)[0]

@@ -287,6 +287,8 @@ def test_bench_torchrun_world8_record_shape():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
+    # the CPU rehearsal also where a GPU is present: eight ranks cannot each take a device of their own there
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "-1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1",
            "--warmup", "0", "--batch-per-gpu", "4", "--window", "6", "--features", "3", "--dataset-windows", "16",
