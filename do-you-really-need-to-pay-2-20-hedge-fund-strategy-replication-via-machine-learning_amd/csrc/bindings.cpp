@@ -530,12 +530,13 @@ std::tuple<Tensor, Tensor> lstm2_fwd(Tensor x, Tensor W, optional<Tensor> b, Ten
 }
 
 
-// W given: also returns dX = dZ W^T (B, T, K) from the same launch; otherwise dX is empty
+// W given: also returns dX = dZ W^T (B, T, K) from the same launch; otherwise dX is empty.  K <= 112: the
+// reverse kernels' seven compute waves own 16 input columns each (columns past 111 would stay unwritten)
 static int check_dx_W(const optional<Tensor>& W, int H) {
   if (!W.has_value()) return 0;
   CHECK_F32(*W);
-  TORCH_CHECK(W->dim() == 2 && W->size(1) == 4 * H && W->size(0) >= 1 && W->size(0) <= 128,
-              "fused dX: W must be (K <= 128, 4H)");
+  TORCH_CHECK(W->dim() == 2 && W->size(1) == 4 * H && W->size(0) >= 1 && W->size(0) <= 112,
+              "fused dX: W must be (K <= 112, 4H)");
   return (int)W->size(0);
 }
 

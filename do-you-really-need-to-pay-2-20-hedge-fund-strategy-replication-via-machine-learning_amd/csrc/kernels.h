@@ -27,7 +27,8 @@ void launch_lstm2_fwd(const void* x, const float* W, const float* b, const float
                       int K, int H, int act, hipStream_t s);
 void launch_lstm2_tfwd(const void* xd, const float* W, const float* U, const void* tape, void* hds, void* ttape, int B,
                        int Tn, int K, int H, int act, hipStream_t s);
-// W / dX non-null: the input gradient dX = dZ W^T (K columns) is produced by the same launch
+// W / dX non-null: the input gradient dX = dZ W^T (K columns) is produced by the same launch; K <= 112 (the
+// seven compute waves own 16 columns each: wider layers take dX from the dgrad GEMM, ops/functional.py)
 // head_d / head_dd + hw: dH (dHdot) = d[b] * hw[t H + h] generated in-kernel (Flatten -> Dense(1) head
 // adjoint); otherwise dH / dHd tensors (nullptr = zeros)
 void launch_lstm2_bwd(const void* dH, const void* tape, const float* U, void* dZ, const float* W, void* dX, int K,

@@ -343,6 +343,13 @@ def _use_lstm2(x: torch.Tensor, U: torch.Tensor) -> bool:
             and not _native.fallback_allowed())
 
 
+def _lstm2_dx_fused(W) -> bool:
+    """Whether the v2 reverse kernels produce dX = dZ W^T in their own launch: their seven compute waves
+    own 16 input columns each, so K <= 112 (csrc/lstm2.hip lstm_tbwd4_kernel).  A wider layer (K <= 128)
+    takes dZ from the launch and dX from the dgrad GEMM, as the fp32 route does."""
+    return W is not None and W.shape[0] <= 112
+
+
 def _use_lstmf(x: torch.Tensor, U: torch.Tensor, act: int) -> bool:
     """fp32 fused-projection kernels (csrc/lstm_f32.hip): H = 100, K in {32, 35, 36, 100}."""
     return (x.dtype == torch.float32 and _nat(x) and not _native.fallback_allowed()
@@ -418,11 +425,14 @@ def lstm_layer_bwd(dH, tape, U, act: int, W=None, need_dz: bool = True):
             dZ = _ops().lstmf_bwd(None if dH is None else dH.contiguous(), tape.t, U, int(act), tape.B, tape.T)
         return dZ if W is None else (dZ, linear_dgrad(dZ, W))
     if isinstance(tape, torch.Tensor):
-        nd = bool(need_dz or W is None)
+        Wk = W if _lstm2_dx_fused(W) else None
+        nd = bool(need_dz or Wk is None)
         if isinstance(dH, OuterAdjoint):  # head adjoint generated in-kernel
-            dZ, dX = _ops().lstm2_bwd(None, tape, U, int(act), W, nd, dH.d.contiguous(), dH.w.reshape(-1).contiguous())
+            dZ, dX = _ops().lstm2_bwd(None, tape, U, int(act), Wk, nd, dH.d.contiguous(), dH.w.reshape(-1).contiguous())
         else:
-            dZ, dX = _ops().lstm2_bwd(dH.contiguous(), tape, U, int(act), W, nd)
+            dZ, dX = _ops().lstm2_bwd(dH.contiguous(), tape, U, int(act), Wk, nd)
+        if W is not None and Wk is None:
+            dX = linear_dgrad(dZ, W)
         if W is not None and not need_dz:
             dZ = None
         return dZ if W is None else (dZ, dX)
@@ -485,19 +495,22 @@ def lstm_layer_tbwd(dH, dHd, tape, ttape, U, act: int, W=None):
         return (dZ, dZd) if W is None else (dZ, dZd, linear_dgrad(dZ, W), linear_dgrad(dZd, W))
     if isinstance(tape, torch.Tensor):
         heads = [a for a in (dH, dHd) if isinstance(a, OuterAdjoint)]
+        Wk = W if _lstm2_dx_fused(W) else None
         # the in-kernel generated head adjoint, also with the fused input gradient (the DX + GEN
         # tangent reverse drifted run to run in r01-r02: a cross-opcode MFMA SrcC hazard, fixed in r03,
         # profiles/r03_race/README.md)
         if heads and all(a is None or (isinstance(a, OuterAdjoint) and a.w is heads[0].w)
                                        for a in (dH, dHd)):
             w = heads[0].w.reshape(-1).contiguous()
-            dZ, dZd, dX, dXd = _ops().lstm2_tbwd(None, None, tape, ttape, U, int(act), W,
+            dZ, dZd, dX, dXd = _ops().lstm2_tbwd(None, None, tape, ttape, U, int(act), Wk,
                                                  None if dH is None else dH.d.contiguous(),
                                                  None if dHd is None else dHd.d.contiguous(), w)
         else:
             dH, dHd = _mat(dH), _mat(dHd)
             dZ, dZd, dX, dXd = _ops().lstm2_tbwd(None if dH is None else dH.contiguous(), dHd.contiguous(), tape,
-                                                 ttape, U, int(act), W)
+                                                 ttape, U, int(act), Wk)
+        if W is not None and Wk is None:
+            dX, dXd = linear_dgrad(dZ, W), linear_dgrad(dZd, W)
         return (dZ, dZd) if W is None else (dZ, dZd, dX, dXd)
     dH, dHd = _mat(dH), _mat(dHd)
     gates, cs = tape

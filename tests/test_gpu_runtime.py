@@ -162,6 +162,29 @@ def test_poisoned_outputs_all_written(cuda, key, dtype):
         ops.set_debug_poison(prev)
 
 
+@pytest.mark.parametrize("F", [20, 120])
+@pytest.mark.parametrize("dtype", ["bfloat16", "float32"])
+def test_poisoned_outputs_all_written_generic_features(cuda, dtype, F):
+    """The poison run at feature counts off the kernels' specialised widths: the runtime-K path of the
+    fused bf16 LSTM kernels (F = 120: the critic's input gradient past the fused 112 columns, which the
+    gradient penalty differentiates through) and the unfused fp32 route."""
+    from hfrep.ops import _native
+
+    ops = _native.native()
+    prev = ops.set_debug_poison(True)
+    try:
+        tr = _trainer(cuda, dtype=dtype, key=("lstm", "wgan_gp"), B=37, T=5, F=F)
+        for _ in range(2):
+            tr.train_step()
+        torch.cuda.synchronize()
+        rec = tr.losses()
+        assert all(np.isfinite(v) for k, v in rec.items() if k != "iteration"), rec
+        for m in (tr.generator, tr.critic):
+            assert bool(torch.isfinite(m.flat).all()), m.model_name
+    finally:
+        ops.set_debug_poison(prev)
+
+
 def test_legacy_script_train_uses_graph(cuda, tmp_path):
     """The reference entry point (GAN/MTSS_WGAN_GP.py -> compat.legacy_gan WGAN_GP.train) replays
     the step from a hipGraph on the GPU; the result is bitwise the eager run's."""

@@ -359,7 +359,7 @@ def test_lstm2_fused_layer(cuda, act, B, T, K):
     dZ = Fn.lstm_layer_bwd(dH.to(cuda), tape, U.to(cuda), act)
     rdz = R.lstm_seq_bwd(dH.double(), rg, rc, U.double(), act)
     _close(dZ, rdz, torch.bfloat16)
-    # fused input gradient: dX = dZ W^T from the same launch (K <= 128)
+    # fused input gradient: dX = dZ W^T from the same launch (K <= 112)
     dZ1, dX = Fn.lstm_layer_bwd(dH.to(cuda), tape, U.to(cuda), act, W=W.to(cuda))
     assert torch.equal(dZ1, dZ)
     _close(dX, rdz @ W.double().t(), torch.bfloat16, scale=(rdz.abs() @ W.double().abs().t()).max().item())
