@@ -11,11 +11,20 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
 #include "kernels.h"
+#include "poison.h"
 
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+
+std::atomic<bool>& hfrep::poison_flag() {
+  static std::atomic<bool> f{[] {
+    const char* e = getenv("HFREP_POISON");
+    return e && e[0] == '1';
+  }()};
+  return f;
+}
 
 namespace {
 
@@ -41,24 +50,10 @@ inline void same_dt(const Tensor& a, const Tensor& b) {
 }
 inline const void* ptr_or_null(const optional<Tensor>& t) { return t.has_value() ? t->data_ptr() : nullptr; }
 
-// Debug poison mode (HFREP_POISON=1 or set_debug_poison(True)): every op output / workspace is
-// allocated filled with NaN instead of uninitialised, so an element a kernel fails to write shows
-// up as a non-finite loss or gradient (tests/test_gpu_runtime.py).  Off by default (it costs a
-// fill per output).  Tapes are exempt: their padded unit lanes are unwritten by design and never
-// read.
-std::atomic<bool>& poison_flag() {
-  static std::atomic<bool> f{[] {
-    const char* e = getenv("HFREP_POISON");
-    return e && e[0] == '1';
-  }()};
-  return f;
-}
-inline Tensor out_empty(at::IntArrayRef sizes, const at::TensorOptions& o) {
-  return poison_flag().load(std::memory_order_relaxed) ? at::full(sizes, NAN, o) : at::empty(sizes, o);
-}
-inline Tensor out_empty_like(const Tensor& t) {
-  return poison_flag().load(std::memory_order_relaxed) ? at::full_like(t, NAN) : at::empty_like(t);
-}
+// Debug poison mode (poison.h): the NaN-filling output allocator, shared with bindings_mlp.cpp
+using hfrep::out_empty;
+using hfrep::out_empty_like;
+using hfrep::poison_flag;
 bool set_debug_poison(bool on) { return poison_flag().exchange(on); }
 
 // ------------------------------------------------------------------------------------ GEMM

@@ -6,6 +6,7 @@
 // master views of the flat parameter buffer, passed as a list in model order:
 //   generator gp = [W1 (F,H), b1, gamma1, beta1, W2 (H,H), b2, gamma2, beta2, W3 (H,F), b3]
 //   critic    cp = [W1 (F,H), b1, W2 (H,H), b2, w3 (T*H or H, 1), b3 (1)]
+//   clip critic cp = [W1 (F,H), b1, gamma1, beta1, W2 (H,H), b2, gamma2, beta2, w3 (H, 1), b3 (1)]
 #include <torch/extension.h>
 #include <torch/library.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -13,6 +14,7 @@
 
 #include "kernels.h"
 #include "mlp.h"
+#include "poison.h"
 
 #include <tuple>
 #include <vector>
@@ -339,6 +341,62 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mlp_gen_bwd(Tensor noise, Ten
   return {dz1, u1, dz2, u2, lnslab};
 }
 
+// ---- clipped WGAN critic (GAN/WGAN.py): outputs, slabs and workspaces through the poison allocator ----
+hfrep::MlpClip clip_of(const std::vector<Tensor>& p, int64_t F, int64_t H) {
+  TORCH_CHECK(p.size() == 10, "mlp ops: clip critic weights [W1, b1, g1, be1, W2, b2, g2, be2, w3, b3]");
+  return hfrep::MlpClip{w(p[0], F * H, "W1"), w(p[1], H, "b1"), w(p[2], H, "gamma1"), w(p[3], H, "beta1"),
+                        w(p[4], H * H, "W2"), w(p[5], H, "b2"), w(p[6], H, "gamma2"), w(p[7], H, "beta2"),
+                        w(p[8], H, "w3"), w(p[9], 1, "b3")};
+}
+inline Tensor slab_new_p(const Tensor& like, int64_t M, int64_t L) {
+  return hfrep::out_empty({(int64_t)hfrep::mlp_slab_rows(M), L}, like.options().dtype(at::kFloat));
+}
+
+// one critic update's gradients on x with `label`: adds the LayerNorm and head gradients into the fp32
+// views cg = [gW1, gb1, gg1, gbe1, gW2, gb2, gg2, gbe2, gw3, gb3] (fixed-order slab sums) and returns
+// the weight-gradient operands (u1, dz2, dz1) of gW2 / gW1 (linear_wgrad_: X = u1 / x) and the loss slab
+std::tuple<Tensor, Tensor, Tensor, Tensor> mlp_wgan_critic(Tensor x, std::vector<Tensor> cp, double label,
+                                                           std::vector<Tensor> cg) {
+  const int dt = act_dt(x);
+  const int64_t F = x.size(-1), H = hidden_of(cp, F), M = rows_of(x, F, "x"), B = x.size(0), T = x.size(1);
+  const auto cr = clip_of(cp, F, H);
+  TORCH_CHECK(M > 0, "mlp_wgan_critic: empty batch");
+  TORCH_CHECK(cg.size() == 10, "mlp_wgan_critic: 10 gradient views");
+  const int64_t n[10] = {F * H, H, H, H, H * H, H, H, H, H, 1};
+  float* p[10];
+  for (int i = 0; i < 10; ++i) {
+    TORCH_CHECK(cg[i].device() == x.device(), "mlp_wgan_critic: gradients on the activations' device");
+    p[i] = const_cast<float*>(w(cg[i], n[i], "critic gradient"));
+  }
+  GUARD(x);
+  Tensor u1 = hfrep::out_empty({B, T, H}, x.options()), dz2 = hfrep::out_empty({B, T, H}, x.options());
+  Tensor dz1 = hfrep::out_empty({B, T, H}, x.options());
+  Tensor lnslab = slab_new_p(x, M, 4 * H), hslab = slab_new_p(x, M, H + 1), slab = slab_new_p(x, M, 2);
+  const hipStream_t s = cur_stream(x);
+  hfrep::launch_mlp_wgan_critic(dt, x.data_ptr(), cr, (float)label, u1.data_ptr(), dz2.data_ptr(), dz1.data_ptr(),
+                                lnslab.data_ptr<float>(), hslab.data_ptr<float>(), slab.data_ptr<float>(), M, (int)F,
+                                (int)H, s);
+  const int P = (int)lnslab.size(0);
+  hfrep::launch_mlp_slab_sum4(lnslab.data_ptr<float>(), P, (int)H, p[2], p[3], p[6], p[7], s);
+  hfrep::launch_mlp_slab_sum_cols(hslab.data_ptr<float>(), P, H + 1, 0, (int)H, p[8], s);
+  hfrep::launch_mlp_slab_sum_cols(hslab.data_ptr<float>(), P, H + 1, (int)H, 1, p[9], s);
+  return {u1, dz2, dz1, slab};
+}
+
+// the generator step's dfake = d mean(-s) / dx through the frozen clip critic, and its loss slab
+std::tuple<Tensor, Tensor> mlp_wgan_critic_dx(Tensor x, std::vector<Tensor> cp) {
+  const int dt = act_dt(x);
+  const int64_t F = x.size(-1), H = hidden_of(cp, F), M = rows_of(x, F, "x");
+  const auto cr = clip_of(cp, F, H);
+  TORCH_CHECK(M > 0, "mlp_wgan_critic_dx: empty batch");
+  GUARD(x);
+  Tensor dx = hfrep::out_empty_like(x);
+  Tensor slab = slab_new_p(x, M, 2);
+  hfrep::launch_mlp_wgan_critic_dx(dt, x.data_ptr(), cr, dx.data_ptr(), slab.data_ptr<float>(), M, (int)F, (int)H,
+                                   cur_stream(x));
+  return {dx, slab};
+}
+
 Tensor mlp_finish(Tensor slab, optional<Tensor> e, int64_t mode, double invB, optional<Tensor> b3, double lam) {
   TORCH_CHECK(slab.is_cuda() && slab.scalar_type() == at::kFloat && slab.is_contiguous() && slab.dim() == 2 &&
                   slab.size(1) == 2,
@@ -392,6 +450,8 @@ TORCH_LIBRARY_FRAGMENT(hfrep, m) {
   m.def("mlp_gan_critic_g(Tensor x, Tensor[] cp, float label, Tensor(a!)[] cg) -> Tensor");
   m.def("mlp_critic_dx(Tensor x, Tensor[] cp, int head, float label) -> (Tensor, Tensor)");
   m.def("mlp_gan_critic(Tensor x, Tensor[] cp, float label) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("mlp_wgan_critic(Tensor x, Tensor[] cp, float label, Tensor(a!)[] cg) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("mlp_wgan_critic_dx(Tensor x, Tensor[] cp) -> (Tensor, Tensor)");
   m.def("mlp_gen_bwd(Tensor noise, Tensor dfake, Tensor[] gp) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("mlp_finish(Tensor slab, Tensor? e, int mode, float invB, Tensor? b3, float lam) -> Tensor");
   m.def("mlp_slab_sum_(Tensor slab, int L, Tensor(a!)? o0, Tensor(b!)? o1=None, Tensor(c!)? o2=None, "
@@ -412,6 +472,8 @@ TORCH_LIBRARY_IMPL(hfrep, CUDA, m) {
   m.impl("mlp_critic_dx", &mlp_critic_dx);
   m.impl("mlp_gan_critic", &mlp_gan_critic);
   m.impl("mlp_gen_bwd", &mlp_gen_bwd);
+  m.impl("mlp_wgan_critic", &mlp_wgan_critic);
+  m.impl("mlp_wgan_critic_dx", &mlp_wgan_critic_dx);
   m.impl("mlp_finish", &mlp_finish);
   m.impl("mlp_slab_sum_", &mlp_slab_sum_);
 }

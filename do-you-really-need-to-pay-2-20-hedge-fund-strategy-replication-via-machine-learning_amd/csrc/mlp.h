@@ -1,5 +1,6 @@
 // Fused MLP-GAN passes (csrc/mlp.hip): host launchers for BASELINE configs 3 / 4 (the vanilla GAN of
-// GAN/GAN.py and the MLP WGAN-GP of GAN/WGAN_GP.py).  Included only by mlp.hip and bindings.cpp.
+// GAN/GAN.py and the MLP WGAN-GP of GAN/WGAN_GP.py) and the clipped MLP WGAN of GAN/WGAN.py.  Included
+// only by mlp.hip and bindings_mlp.cpp.
 //
 // Every launcher takes the fp32 master weights (Keras layout: kernel (in, out), row-major) and
 // activations of dtype `dt` (DT_F32 / DT_BF16) as row-major (M, features) matrices, M = B * T rows.
@@ -24,6 +25,12 @@ struct MlpGen {
 // (w3: T*H), head 1 = per-row Dense(1, sigmoid) (w3: H)
 struct MlpCritic {
   const float *W1, *b1, *W2, *b2, *w3, *b3;
+};
+
+// clipped WGAN critic (GAN/WGAN.py), per row: Dense(H) -> LReLU -> LN -> Dense(H) -> LReLU -> LN -> Dense(1)
+// (w3: H, b3: 1)
+struct MlpClip {
+  const float *W1, *b1, *g1, *be1, *W2, *b2, *g2, *be2, *w3, *b3;
 };
 
 void launch_mlp_gen_fwd(int dt, const void* noise, const MlpGen& g, void* out, int64_t M, int F, int H,
@@ -52,9 +59,19 @@ void launch_mlp_gan_critic(int dt, const void* x, const MlpCritic& cr, float lab
 // dgamma2, dbeta2)
 void launch_mlp_gen_bwd(int dt, const void* noise, const void* dfake, const MlpGen& g, void* dz1, void* u1,
                         void* dz2, void* u2, float* lnslab, int64_t M, int F, int H, hipStream_t s);
+// one update of the clipped WGAN critic on x with `label` (loss = mean over the M rows of label * s_r):
+// wgrad operands u1 (X of W2), dz2 (dY of W2), dz1 (dY of W1; its X is x); per-wave partials, one row
+// per wave (mlp_slab_rows(M) rows, every row written): lnslab (4 H: dgamma1, dbeta1, dgamma2, dbeta2),
+// hslab (H + 1: gw3 | gb3), slab (2: sum of label * s_r | 0; launch_mlp_finish mode 2 with 1 / M)
+void launch_mlp_wgan_critic(int dt, const void* x, const MlpClip& cr, float label, void* u1, void* dz2, void* dz1,
+                            float* lnslab, float* hslab, float* slab, int64_t M, int F, int H, hipStream_t s);
+// the generator step's input gradient through that critic: dx = d mean(-s) / dx; slab (2: sum of -s_r | 0)
+void launch_mlp_wgan_critic_dx(int dt, const void* x, const MlpClip& cr, void* dx, float* slab, int64_t M, int F,
+                               int H, hipStream_t s);
 // fixed-order reduction of a loss slab (P rows x 2) and optional per-sample e (n_e values) into
 // out[4]: mode 0 = WGAN-GP critic pack [w_real + w_fake + lam pen, w_real, w_fake, pen];
-// mode 1 = generator loss [loss, 0, 0, 0] (W: -mean score; BCE: mean); mode 2 = BCE segment loss [loss, 0, 0, 0]
+// mode 1 = generator loss [loss, 0, 0, 0] (W: -mean score; BCE: mean); mode 2 = mean of the per-row losses
+// in slab column 0 [loss, 0, 0, 0] (BCE segments; the clip WGAN's label * s_r and -s_r)
 void launch_mlp_finish(const float* slab, int P, const float* e, int64_t n_e, int mode, float invB, const float* b3,
                        float lam, float* out, hipStream_t s);
 // fixed-order column sums of a (P, L) slab added into out[L]; the 4-segment form adds segment k of

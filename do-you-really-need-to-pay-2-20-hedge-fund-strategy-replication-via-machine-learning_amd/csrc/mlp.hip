@@ -26,6 +26,11 @@
 // reverse-over-tangent of the gradient penalty all have adjoints along the same head vector w3_t, so
 // their weight-gradient operands are summed per row before they leave the kernel (X2c, X1c, Y3c
 // below) and each weight gets ONE streaming wgrad instead of three.
+//
+// The clipped WGAN of GAN/WGAN.py:147-205 has the generator's Dense -> LReLU -> LN skeleton in its critic
+// (linear Dense layers, per-row Dense(1) head, no Flatten), so its two passes compose the same blocks:
+// mlp_wgan_critic (one critic update on one batch with its label: wgrad operands u1 / dz2 / dz1, LayerNorm
+// and head gradients as per-wave column-sum slabs) and mlp_wgan_critic_dx (the generator step's dfake).
 #include "common.h"
 #include "kernels.h"
 #include "mfma.h"
@@ -1385,8 +1390,9 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_gan_critic_kernel(const T* __
 // LayerNorm -> LeakyReLU -> sigmoid reverse of one row (the generator's Dense(sigmoid) + LReLU + LN
 // blocks): g = dL/du (LN output gradient), y = the sigmoid outputs, (mean, rstd) of lrelu(y); writes
 // dL/dz into out (may alias g or y: element-wise after the row sums) and adds the gamma-gradient
-// column sums (sum_r g * xhat) into pg
-template <int N>
+// column sums (sum_r g * xhat) into pg.  ACT = ACT_LINEAR: the clip critic's Dense(linear) + LReLU + LN
+// blocks (y = the Dense outputs, no sigmoid factor); PG = false: no parameter gradients (pg unused).
+template <int N, int ACT = ACT_SIGMOID, bool PG = true>
 __device__ __forceinline__ void ln_reverse(const f32x16* g, const f32x16* y, f32x16* out, const float* gam, float mean,
                                            float rstd, int h, int lane, float* pg) {
   constexpr int NT = (N + 31) / 32;
@@ -1431,10 +1437,11 @@ __device__ __forceinline__ void ln_reverse(const f32x16* g, const f32x16* y, f32
         px[q] = dv * xh;
         float dl = rstd * (dv * gg[e] - m1 - xh * m2);
         dl *= yv >= 0.f ? 1.f : LRELU_ALPHA_F;
-        out[t][q] = in ? dl * yv * (1.f - yv) : 0.f;
+        if constexpr (ACT == ACT_SIGMOID) out[t][q] = in ? dl * yv * (1.f - yv) : 0.f;
+        else out[t][q] = in ? dl : 0.f;
       }
     }
-    pg[t] += colsum(px, lane);
+    if constexpr (PG) pg[t] += colsum(px, lane);
   }
 }
 
@@ -1846,6 +1853,173 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_gen_bwd_w_kernel(const bf16_t
 }
 
 // ===================================================================================================
+// clipped WGAN critic (GAN/WGAN.py:147-158): per row Dense(H) -> LReLU -> LN -> Dense(H) -> LReLU -> LN
+// -> Dense(1); W loss mean over the M rows of label * s_r (label -1 real, +1 fake; loop :166-205)
+// ===================================================================================================
+// LDS vectors of both kernels: b1 | gamma1 | beta1 | b2 | gamma2 | beta2 | w3
+constexpr int CLIP_VECS = 7;
+
+// this lane's row through the critic: x -> u2 (in a), the Dense 2 outputs z2 (in y2), the row statistics
+// of both LayerNorms and the score s (without b3).  U1: also store u1 = LN1's output (X operand of gW2).
+template <typename T, int F, int H, bool U1>
+__device__ __forceinline__ float clip_forward(const f32x16* x, f32x16* a, f32x16* y2,
+                                              const typename MP<T>::frag* f1, const typename MP<T>::frag* f2,
+                                              const float* vec, T* __restrict__ u1o, int64_t row, int64_t M, int lane,
+                                              int h, float& mean1, float& rstd1, float& mean2, float& rstd2) {
+  constexpr int NTH = (H + 31) / 32;
+  dense<T, F, H>(x, a, f1, lane);
+  bias_act<H>(a, vec + 0 * VEC, ACT_LINEAR, h);
+  lrelu_ln<H>(a, vec + 1 * VEC, vec + 2 * VEC, h, mean1, rstd1);
+  if constexpr (U1) store_rows<T, H>(u1o, row, M, a, h);
+  dense<T, H, H>(a, y2, f2, lane);
+  bias_act<H>(y2, vec + 3 * VEC, ACT_LINEAR, h);
+#pragma unroll
+  for (int t = 0; t < NTH; ++t) a[t] = y2[t];
+  lrelu_ln<H>(a, vec + 4 * VEC, vec + 5 * VEC, h, mean2, rstd2);
+  return rowdot<H>(a, vec + 6 * VEC, true, h);
+}
+
+// One critic update's gradients on one batch x with `label`: ds_r = label / M for every row.  Writes
+// the streaming weight-gradient operands u1 (X of gW2), dz2 (dY of gW2), dz1 (dY of gW1; its X is x),
+// the per-wave LayerNorm partials (lnslab rows: dgamma1 | dbeta1 | dgamma2 | dbeta2, as mlp_gen_bwd), the
+// per-wave head partials (hslab rows: gw3 = sum_r ds_r u2_r (H) | gb3 = sum_r ds_r) and the loss slab
+// (column 0: sum_r label * s_r).  Rows past M carry ds = 0: every adjoint of theirs is zero.  y1 is
+// recomputed in the reverse (register budget, as mlp_gen_bwd).
+template <typename T, int F, int H>
+__global__ void __launch_bounds__(MLP_THREADS) mlp_wgan_critic_kernel(const T* __restrict__ x, MlpClip c, float label,
+                                                                      T* __restrict__ u1o, T* __restrict__ dz2o,
+                                                                      T* __restrict__ dz1o, float* __restrict__ lnslab,
+                                                                      float* __restrict__ hslab,
+                                                                      float* __restrict__ slab, int64_t M, float inv) {
+  using Fr = typename MP<T>::frag;
+  constexpr int NTH = (H + 31) / 32, NTF = (F + 31) / 32;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  Fr* f1 = reinterpret_cast<Fr*>(lds);
+  Fr* f2 = f1 + fwd_entries<T, F, H>() * 64;
+  Fr* d2 = f2 + fwd_entries<T, H, H>() * 64;
+  float* vec = reinterpret_cast<float*>(d2 + dgrad_entries<T, H, H>() * 64);
+  build_fwd<T, F, H>(f1, c.W1);
+  build_fwd<T, H, H>(f2, c.W2);
+  build_dgrad<T, H, H>(d2, c.W2);
+  load_vec(vec + 0 * VEC, c.b1, H); load_vec(vec + 1 * VEC, c.g1, H); load_vec(vec + 2 * VEC, c.be1, H);
+  load_vec(vec + 3 * VEC, c.b2, H); load_vec(vec + 4 * VEC, c.g2, H); load_vec(vec + 5 * VEC, c.be2, H);
+  load_vec(vec + 6 * VEC, c.w3, H);
+  __syncthreads();
+  const float b3 = c.b3[0];
+  const float* gam1 = vec + 1 * VEC;
+  const float* gam2 = vec + 4 * VEC;
+  float pg1[NTH], pb1[NTH], pg2[NTH], pb2[NTH], pw3[NTH];  // per-lane column sums (see colsum)
+#pragma unroll
+  for (int t = 0; t < NTH; ++t) pg1[t] = pb1[t] = pg2[t] = pb2[t] = pw3[t] = 0.f;
+  float acc = 0.f, sds = 0.f;
+  MLP_LOOP {
+    const int64_t row = tile * 32 + (lane & 31);
+    const bool ok = row < M;
+    const float ds = ok ? label * inv : 0.f;
+    f32x16 xr[NTF], a[NTH], y2[NTH], d[NTH];
+    float mean1, rstd1, mean2, rstd2;
+    // ---- forward (u1 out; z2 and the row statistics kept)
+    load_rows<T, F>(xr, x, row, M, h);
+    const float sc =
+        clip_forward<T, F, H, true>(xr, a, y2, f1, f2, vec, u1o, row, M, lane, h, mean1, rstd1, mean2, rstd2) + b3;
+    if (ok && h == 0) {
+      acc += label * sc;
+      sds += ds;
+    }
+    // ---- head: gw3 += ds u2; du2 = ds w3 (rank 1)
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) {
+      a[t] *= ds;
+      pw3[t] += colsum(a[t], lane);
+    }
+    head_rows<H>(d, vec + 6 * VEC, ds, ok, h);
+    // ---- LN2 / LReLU reverse -> dz2
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) pb2[t] += colsum(d[t], lane);
+    ln_reverse<H, ACT_LINEAR>(d, y2, d, gam2, mean2, rstd2, h, lane, pg2);
+    store_rows<T, H>(dz2o, row, M, d, h);
+    // ---- du1 = dz2 W2^T; recompute y1; LN1 / LReLU reverse -> dz1
+    dense<T, H, H>(d, y2, d2, lane);  // y2 now holds du1
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) pb1[t] += colsum(y2[t], lane);
+    dense<T, F, H>(xr, a, f1, lane);
+    bias_act<H>(a, vec + 0 * VEC, ACT_LINEAR, h);  // y1
+    ln_reverse<H, ACT_LINEAR>(y2, a, a, gam1, mean1, rstd1, h, lane, pg1);
+    store_rows<T, H>(dz1o, row, M, a, h);
+  }
+  // per-wave partials: lanes with bit 0 clear own feature featq(colsum_q(lane), h) of every tile
+  const int64_t wv = (int64_t)blockIdx.x * MLP_WAVES + (threadIdx.x >> 6);
+  float* out = lnslab + wv * 4 * H;
+  float* hout = hslab + wv * (H + 1);
+  if ((lane & 1) == 0) {
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) {
+      const int f = 32 * t + featq(colsum_q(lane), h);
+      if (f < H) {
+        out[f] = pg1[t];
+        out[H + f] = pb1[t];
+        out[2 * H + f] = pg2[t];
+        out[3 * H + f] = pb2[t];
+        hout[f] = pw3[t];
+      }
+    }
+  }
+  sds = wave_sum(sds);
+  if (lane == 0) hout[H] = sds;
+  slab_put(slab, 2, 0, acc);
+  slab_put(slab, 2, 1, 0.f);
+}
+
+// The generator step's dfake through the frozen critic: the same forward, ds_r = -1 / M (loss
+// mean(-s)), reverse down to dx = dz1 W1^T.  No parameter gradients.  slab column 0: sum_r -s_r.
+template <typename T, int F, int H>
+__global__ void __launch_bounds__(MLP_THREADS) mlp_wgan_critic_dx_kernel(const T* __restrict__ x, MlpClip c,
+                                                                         T* __restrict__ dx, float* __restrict__ slab,
+                                                                         int64_t M, float inv) {
+  using Fr = typename MP<T>::frag;
+  constexpr int NTH = (H + 31) / 32, NTF = (F + 31) / 32;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  Fr* f1 = reinterpret_cast<Fr*>(lds);
+  Fr* f2 = f1 + fwd_entries<T, F, H>() * 64;
+  Fr* d2 = f2 + fwd_entries<T, H, H>() * 64;
+  Fr* d1 = d2 + dgrad_entries<T, H, H>() * 64;
+  float* vec = reinterpret_cast<float*>(d1 + dgrad_entries<T, F, H>() * 64);
+  build_fwd<T, F, H>(f1, c.W1);
+  build_fwd<T, H, H>(f2, c.W2);
+  build_dgrad<T, H, H>(d2, c.W2);
+  build_dgrad<T, F, H>(d1, c.W1);
+  load_vec(vec + 0 * VEC, c.b1, H); load_vec(vec + 1 * VEC, c.g1, H); load_vec(vec + 2 * VEC, c.be1, H);
+  load_vec(vec + 3 * VEC, c.b2, H); load_vec(vec + 4 * VEC, c.g2, H); load_vec(vec + 5 * VEC, c.be2, H);
+  load_vec(vec + 6 * VEC, c.w3, H);
+  __syncthreads();
+  const float b3 = c.b3[0];
+  const float* gam1 = vec + 1 * VEC;
+  const float* gam2 = vec + 4 * VEC;
+  float acc = 0.f;
+  MLP_LOOP {
+    const int64_t row = tile * 32 + (lane & 31);
+    const bool ok = row < M;
+    f32x16 xr[NTF], a[NTH], y2[NTH], d[NTH];
+    float mean1, rstd1, mean2, rstd2;
+    load_rows<T, F>(xr, x, row, M, h);
+    const float sc = clip_forward<T, F, H, false>(xr, a, y2, f1, f2, vec, static_cast<T*>(nullptr), row, M, lane, h,
+                                                  mean1, rstd1, mean2, rstd2) + b3;
+    if (ok && h == 0) acc -= sc;
+    head_rows<H>(d, vec + 6 * VEC, -inv, ok, h);  // du2
+    ln_reverse<H, ACT_LINEAR, false>(d, y2, d, gam2, mean2, rstd2, h, lane, nullptr);
+    dense<T, H, H>(d, y2, d2, lane);  // du1
+    load_rows<T, F>(xr, x, row, M, h);  // (reloaded, not held across the reverse: register budget)
+    dense<T, F, H>(xr, a, f1, lane);
+    bias_act<H>(a, vec + 0 * VEC, ACT_LINEAR, h);  // y1
+    ln_reverse<H, ACT_LINEAR, false>(y2, a, a, gam1, mean1, rstd1, h, lane, nullptr);
+    dense<T, H, F>(a, xr, d1, lane);  // dx
+    store_rows<T, F>(dx, row, M, xr, h);
+  }
+  slab_put(slab, 2, 0, acc);
+  slab_put(slab, 2, 1, 0.f);
+}
+
+// ===================================================================================================
 // fixed-order reductions
 // ===================================================================================================
 __global__ void __launch_bounds__(256) mlp_finish_kernel(const float* __restrict__ slab, int P,
@@ -1974,6 +2148,16 @@ template <typename T, int F, int H> constexpr size_t lds_gen_bwd() {
              frag_bytes<T>() +
          6 * VEC * 4;
 }
+// clip critic: forward W1 / W2 and dgrad W2 images (+ dgrad W1 for the input gradient), 7 vectors
+template <typename T, int F, int H> constexpr size_t lds_wgan_critic() {
+  return (size_t)(fwd_entries<T, F, H>() + fwd_entries<T, H, H>() + dgrad_entries<T, H, H>()) * frag_bytes<T>() +
+         CLIP_VECS * VEC * 4;
+}
+template <typename T, int F, int H> constexpr size_t lds_wgan_critic_dx() {
+  return lds_wgan_critic<T, F, H>() + (size_t)dgrad_entries<T, F, H>() * frag_bytes<T>();
+}
+static_assert(lds_wgan_critic<float, 36, 100>() <= 160 * 1024, "fp32 clip critic images exceed LDS");
+static_assert(lds_wgan_critic_dx<float, 36, 100>() <= 160 * 1024, "fp32 clip critic input-gradient images exceed LDS");
 static_assert(lds_critic4<float, 36, 100>() <= 160 * 1024, "fp32 critic images exceed LDS");
 static_assert(lds_gen_bwd<float, 36, 100>() <= 160 * 1024, "fp32 generator reverse images exceed LDS");
 
@@ -2129,6 +2313,33 @@ void launch_mlp_gen_bwd(int dt, const void* noise, const void* dfake, const MlpG
     set_lds(k, lds);
     hipLaunchKernelGGL(k, dim3(slab_grid(k, lds, M)), dim3(MLP_THREADS), lds, s, (const T*)noise, (const T*)dfake, g,
                        (T*)dz1, (T*)u1, (T*)dz2, (T*)u2, lnslab, M);
+  });
+  (void)H;
+}
+
+// ---- clipped WGAN critic (both dtypes) ----
+void launch_mlp_wgan_critic(int dt, const void* x, const MlpClip& cr, float label, void* u1, void* dz2, void* dz1,
+                            float* lnslab, float* hslab, float* slab, int64_t M, int F, int H, hipStream_t s) {
+  if (M <= 0) return;
+  MLP_DISPATCH(dt, F, {
+    auto k = mlp_wgan_critic_kernel<T, FF, 100>;
+    constexpr size_t lds = lds_wgan_critic<T, FF, 100>();
+    set_lds(k, lds);
+    hipLaunchKernelGGL(k, dim3(slab_grid(k, lds, M)), dim3(MLP_THREADS), lds, s, (const T*)x, cr, label, (T*)u1,
+                       (T*)dz2, (T*)dz1, lnslab, hslab, slab, M, 1.f / (float)M);
+  });
+  (void)H;
+}
+
+void launch_mlp_wgan_critic_dx(int dt, const void* x, const MlpClip& cr, void* dx, float* slab, int64_t M, int F,
+                               int H, hipStream_t s) {
+  if (M <= 0) return;
+  MLP_DISPATCH(dt, F, {
+    auto k = mlp_wgan_critic_dx_kernel<T, FF, 100>;
+    constexpr size_t lds = lds_wgan_critic_dx<T, FF, 100>();
+    set_lds(k, lds);
+    hipLaunchKernelGGL(k, dim3(slab_grid(k, lds, M)), dim3(MLP_THREADS), lds, s, (const T*)x, cr, (T*)dx, slab, M,
+                       1.f / (float)M);
   });
   (void)H;
 }

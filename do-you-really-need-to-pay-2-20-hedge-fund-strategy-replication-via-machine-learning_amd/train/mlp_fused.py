@@ -1,9 +1,10 @@
-"""Fused MLP-GAN training steps (BASELINE configs 3 / 4) on the kernels of ``csrc/mlp.hip``.
+"""Fused MLP-GAN training steps (BASELINE configs 3 / 4 and the clipped MLP WGAN) on the kernels of
+``csrc/mlp.hip``.
 
 The layer-by-layer engine (``Sequential.efwd / ebwd / etfwd / etbwd``) runs one kernel per layer and
 pass and round-trips every (B*T, 100) activation and adjoint through HBM: 607 GB per bf16 MLP WGAN-GP
-iteration (``profiles/r06_mlp/baseline``).  For the two MLP models of the BASELINE configs this module
-replaces it with one kernel per pass that carries a 32-row tile through every layer in registers:
+iteration (``profiles/r06_mlp/baseline``).  For the three MLP models of the zoo this module replaces it
+with one kernel per pass that carries a 32-row tile through every layer in registers:
 
 * ``mlp_gen_fwd``     G(z) (GAN/WGAN_GP.py:221-236, GAN/GAN.py:127-142);
 * ``mlp_wgp_norm`` + ``mlp_wgp_coef``   the gradient penalty's first-order pass: |dD/dx_hat| per
@@ -19,10 +20,16 @@ replaces it with one kernel per pass that carries a 32-row tile through every la
 * ``mlp_critic_dx`` + ``mlp_gen_bwd``  the generator update through the frozen critic
   (GAN/WGAN_GP.py:178-189, GAN/GAN.py:195-198); in bf16 ``mlp_gen_bwd_w`` accumulates all ten
   generator parameter gradients in the kernel;
+* ``mlp_wgan_critic``  one update of the clipped WGAN's LReLU + LayerNorm critic (GAN/WGAN.py:147-158,
+  loop :166-205) on one batch with its label: forward, rank-1 head adjoint, both LN / LReLU reverses;
+  the weight-gradient operands (u1, dz2, dz1) go to ``linear_wgrad_``, the LayerNorm and head gradients
+  come from per-wave column-sum slabs; ``mlp_wgan_critic_dx`` is the generator step's dfake through that
+  critic (then ``mlp_gen_bwd`` / ``mlp_gen_bwd_w`` as for the other two models);
 
 followed by the streaming weight-gradient kernels (``linear_wgrad_``) and the fused optimizer.  The
 random draws are the engine path's, in its order (real, noise, alpha per critic update), so both paths
-see the same batches; ``HFREP_MLP_FUSED=0`` selects the engine path (A/B, tests).
+see the same batches; ``HFREP_MLP_FUSED=0`` selects the engine path (A/B, tests).  When an MLP trainer on
+a GPU does not get the fused path, one log line (logger ``hfrep.mlp_fused``) names the reason.
 
 For the affine WGAN-GP critic the penalty's input gradient dD/dx_hat does not depend on x_hat, so
 neither x_hat nor D(x_hat) is formed (alpha is still drawn: the RNG stream stays the engine's).  Going
@@ -34,6 +41,7 @@ for every row (``mlp_critic_dx_affine``).  ``HFREP_MLP_AFFINE=0`` keeps the per-
 """
 from __future__ import annotations
 
+import logging
 import os
 
 import torch
@@ -41,6 +49,9 @@ import torch
 from ..models.layers import Dense, Flatten, LayerNormalization, LeakyReLU
 from ..ops import _native
 from ..ops import functional as Fn
+
+
+log = logging.getLogger("hfrep.mlp_fused")
 
 
 def _ops():
@@ -87,14 +98,39 @@ def _critic_lists(C, head: int, grad=False):
             + _views(C, last, ["kernel", "bias"], grad))
 
 
+def _clip_critic_lists(C, grad=False):
+    """[W1, b1, gamma1, beta1, W2, b2, gamma2, beta2, w3, b3] of the clipped WGAN's critic, or None if C
+    is not Dense(linear) -> LReLU(0.2) -> LN(1e-3) -> Dense(linear) -> LReLU(0.2) -> LN(1e-3) -> Dense(1)
+    (per row, no Flatten; every Dense with bias)."""
+    L = C.layers
+    kinds = [Dense, LeakyReLU, LayerNormalization, Dense, LeakyReLU, LayerNormalization, Dense]
+    if len(L) != 7 or not all(isinstance(l, k) for l, k in zip(L, kinds)):
+        return None
+    if not (all(L[i].act_code == 0 and L[i].use_bias for i in (0, 3, 6)) and L[6].units == 1):
+        return None
+    if abs(L[1].alpha - 0.2) > 1e-6 or abs(L[4].alpha - 0.2) > 1e-6 or L[2].eps != 1e-3 or L[5].eps != 1e-3:
+        return None
+    out = []
+    for d, ln in ((L[0], L[2]), (L[3], L[5])):
+        out += _views(C, d, ["kernel", "bias"], grad) + _views(C, ln, ["gamma", "beta"], grad)
+    return out + _views(C, L[6], ["kernel", "bias"], grad)
+
+
+_HEAD = {"wgan_gp": 0, "gan": 1, "wgan": 2}  # 2: the clip critic (per-row LReLU + LN, W loss)
+
+
+def _critic_of(C, head: int, grad=False):
+    return _clip_critic_lists(C, grad) if head == 2 else _critic_lists(C, head, grad)
+
+
 class FusedMLP:
     """The MLP models' training step on the fused kernels (attached to a GANTrainer)."""
 
     def __init__(self, tr):
         self.tr = tr
-        self.head = 0 if tr.cfg.loss == "wgan_gp" else 1
+        self.head = _HEAD[tr.cfg.loss]
         self.gw, self.gg = _gen_lists(tr.generator), _gen_lists(tr.generator, grad=True)
-        self.cw, self.cg = _critic_lists(tr.critic, self.head), _critic_lists(tr.critic, self.head, grad=True)
+        self.cw, self.cg = _critic_of(tr.critic, self.head), _critic_of(tr.critic, self.head, grad=True)
         self._ones = {}
         # GP critic update (both dtypes): rows walked t-major, the weight gradients as per-t column sums
         # in registers (mlp_wgp_critic_t) -- no per-row operands in HBM.  HFREP_MLP_WGRAD_TSUM=0 takes
@@ -116,18 +152,36 @@ class FusedMLP:
         self.gan_colsum = self.head == 1 and os.environ.get("HFREP_MLP_WGRAD_INKERNEL", "1") != "0"
 
     @staticmethod
-    def supported(tr) -> bool:
+    def decline_reason(tr) -> str | None:
+        """Why this trainer does not get the fused path (None: it does)."""
         cfg = tr.cfg
+        if cfg.arch != "mlp" or cfg.loss not in _HEAD:
+            return "not an MLP model of the zoo"
+        if tr.device.type != "cuda":
+            return "device is not a GPU"
         if os.environ.get("HFREP_MLP_FUSED", "1") == "0":
-            return False
-        if cfg.arch != "mlp" or cfg.loss not in ("gan", "wgan_gp") or tr.device.type != "cuda":
-            return False
-        if tr.dtype not in (torch.float32, torch.bfloat16) or _native.fallback_allowed():
-            return False
-        if not _native.available() or not bool(_ops().mlp_supported(int(cfg.features), int(cfg.hidden))):
-            return False
-        head = 0 if cfg.loss == "wgan_gp" else 1
-        return _gen_lists(tr.generator) is not None and _critic_lists(tr.critic, head) is not None
+            return "env switch HFREP_MLP_FUSED=0"
+        if tr.dtype not in (torch.float32, torch.bfloat16):
+            return f"dtype {tr.dtype} (float32 and bfloat16 only)"
+        if _native.fallback_allowed() or not _native.available():
+            return "native library not in use"
+        if not bool(_ops().mlp_supported(int(cfg.features), int(cfg.hidden))):
+            return f"width (F, H) = ({int(cfg.features)}, {int(cfg.hidden)}) not instantiated"
+        if _gen_lists(tr.generator) is None or _critic_of(tr.critic, _HEAD[cfg.loss]) is None:
+            return "structure mismatch (generator or critic is not the zoo's layer sequence)"
+        return None
+
+    @staticmethod
+    def supported(tr) -> bool:
+        why = FusedMLP.decline_reason(tr)
+        if why is None:
+            return True
+        # one line per trainer, for an MLP model on a GPU only (elsewhere the engine is the expected path)
+        if tr.cfg.arch == "mlp" and tr.device.type == "cuda" and not getattr(tr, "_fused_decline_logged", False):
+            tr._fused_decline_logged = True
+            log.warning("fused MLP path declined for (%s, %s): %s; running the layer-by-layer engine",
+                        tr.cfg.arch, tr.cfg.loss, why)
+        return False
 
     def _ones_col(self, n, dtype):
         key = (n, dtype)
@@ -146,6 +200,9 @@ class FusedMLP:
             else:
                 dfake, slab = ops.mlp_critic_dx(fake, self.cw, 0, -1.0)
             loss = ops.mlp_finish(slab, None, 1, 1.0 / B, self.cw[5], 0.0)
+        elif self.head == 2:
+            dfake, slab = ops.mlp_wgan_critic_dx(fake, self.cw)  # slab: sum of -s over the rows
+            loss = ops.mlp_finish(slab, None, 2, 1.0 / noise[..., 0].numel(), None, 0.0)
         else:
             dfake, slab = ops.mlp_critic_dx(fake, self.cw, 1, 1.0)
             loss = ops.mlp_finish(slab, None, 2, 1.0 / noise[..., 0].numel(), None, 0.0)
@@ -196,6 +253,32 @@ class FusedMLP:
         tr._g_acc = self._generator_grads(noise, fake).to(tr._acc)
         tr._apply(tr.generator)
 
+    # ---- clipped WGAN (GAN/WGAN.py) ---------------------------------------------------------------
+    def _wgan_critic_grads(self, x, label: float):
+        """Accumulate the critic gradient of mean(label * C(x)) over the B*T rows; returns the loss."""
+        ops = _ops()
+        u1, dz2, dz1, slab = ops.mlp_wgan_critic(x, self.cw, float(label), self.cg)
+        gW1, gb1, _gg1, _gbe1, gW2, gb2 = self.cg[:6]
+        Fn.linear_wgrad_(x, dz1, gW1, gb1)
+        Fn.linear_wgrad_(u1, dz2, gW2, gb2)
+        return ops.mlp_finish(slab, None, 2, 1.0 / x[..., 0].numel(), None, 0.0)[0]
+
+    def _step_wgan(self):
+        tr, ops = self.tr, _ops()
+        B = tr.cfg.batch_size
+        for _ in range(tr.n_critic):
+            real, noise = tr._batch(B)
+            fake = ops.mlp_gen_fwd(noise, self.gw)
+            lr_ = self._wgan_critic_grads(real, -1.0).to(tr._acc)
+            tr._apply(tr.critic, clip=0.0)
+            lf_ = self._wgan_critic_grads(fake, 1.0).to(tr._acc)
+            tr._apply(tr.critic, clip=tr.clip)
+            tr._d_acc = torch.stack([0.5 * (lr_ + lf_), lr_, lf_, torch.zeros_like(lr_)])
+        # the generator step trains on the last critic update's noise (GAN/WGAN.py:205) with the same
+        # generator weights: its fake windows are that update's
+        tr._g_acc = self._generator_grads(noise, fake).to(tr._acc)
+        tr._apply(tr.generator)
+
     # ---- vanilla GAN (config 3) -------------------------------------------------------------------
     def _gan_d_grads(self, x, label: float):
         """Accumulate the discriminator gradient of BCE(D(x), label) (mean over the B*T rows); returns
@@ -234,5 +317,7 @@ class FusedMLP:
     def train_step(self):
         if self.head == 0:
             self._step_wgan_gp()
+        elif self.head == 2:
+            self._step_wgan()
         else:
             self._step_gan()
