@@ -85,6 +85,14 @@ def _add_train_args(p):
     p.add_argument("--graph", action="store_true", help="replay each iteration from a captured hipGraph")
     p.add_argument("--save-dir", default="./trained_generator")
     p.add_argument("--no-save", action="store_true")
+    p.add_argument("--wdist-every", type=int, default=0,
+                   help="track the W-dist of a fixed generated sample against the held-out real windows (the parity "
+                        "protocol's, seed + 1000) on the device every N iterations and after the last one: "
+                        "w_dist / w_best / w_best_iteration in the log records (0 = off)")
+    p.add_argument("--wdist-n", type=int, default=None,
+                   help="evaluation windows of --wdist-every (default: the preset's n_windows, at most 4096)")
+    p.add_argument("--save-best", default=None,
+                   help="with --wdist-every: write the generator with the best tracked W-dist here (.pkl / .npz)")
     return p
 
 
@@ -131,6 +139,14 @@ def _run_segment(tr, s, a):
     opts = RunOptions(epochs=stop, log_every=s["log_every"], log_path=a.log, echo=not a.quiet,
                       ckpt_dir=a.ckpt_dir, ckpt_every=a.ckpt_every, resume=a.resume, nan_guard=not a.no_nan_guard,
                       graph=graph)
+    if a.save_best and a.wdist_every <= 0:
+        raise SystemExit("--save-best needs --wdist-every")
+    if a.wdist_every > 0:
+        # the parity protocol's hold-out (cmd_parity): a tracked value at the last iteration is its w_fake_vs_real
+        opts.wdist_every = a.wdist_every
+        opts.wdist_real = _dataset(s["data"], s["n_windows"], s["window"], s["features"], s["seed"] + 1000)
+        opts.wdist_n = a.wdist_n if a.wdist_n is not None else min(len(opts.wdist_real), 4096)
+        opts.save_best = a.save_best if stop >= s["epochs"] else None
     recs = run(tr, opts)
     if tr.iteration < s["epochs"]:
         checkpoint_now(tr, opts)
@@ -151,7 +167,10 @@ def cmd_train(a) -> int:
         prefix = tr.cfg.entry().save_prefix or "GEN"
         path = os.path.join(a.save_dir, f"{prefix}{checkpoint.timestamp()}.pkl")
         checkpoint.save_generator(path, tr.generator, dict(tr.cfg.__dict__))
-        print(json.dumps({"saved": path, "iterations": tr.iteration, "last": recs[-1] if recs else None}))
+        out = {"saved": path, "iterations": tr.iteration, "last": recs[-1] if recs else None}
+        if a.save_best:
+            out["saved_best"] = a.save_best
+        print(json.dumps(out))
     return 0
 
 
@@ -263,6 +282,9 @@ def cmd_parity(a) -> int:
     res.update(model=a.model, preset=a.preset, iterations=tr.iteration, dtype=s["dtype"],
                batch_size=s["batch_size"], world=tr.world, seed=s["seed"],
                device=torch.cuda.get_device_name() if tr.device.type == "cuda" else "cpu")
+    if getattr(tr, "wdist_tracker", None) is not None:
+        v = tr.wdist_tracker.values()
+        res.update(w_tracked_last=v["w_dist"], w_tracked_best=v["w_best"], w_best_iteration=v["w_best_iteration"])
     if a.preset == "reference" and s["window"] == 48 and s["features"] == 35 and s["data"] == "cleaned":
         try:  # the reference's own trained generator under the same protocol (absent data: skipped)
             anc = reference_anchor(seed=s["seed"])

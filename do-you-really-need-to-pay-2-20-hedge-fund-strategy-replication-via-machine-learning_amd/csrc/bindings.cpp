@@ -933,6 +933,29 @@ void clip_(Tensor p, double c) {
   hfrep::launch_clip(p.data_ptr<float>(), p.numel(), (float)c, cur_stream(p));
 }
 
+// ------------------------------------------------------------------------------------ W-dist
+// (F + 1) float64: W1 of every column of x (n, F) against the ascending rows of ref_sorted (F, n), then
+// the mean over the columns (csrc/wdist.hip); stream-ordered, no host synchronise
+Tensor wdist_sorted(Tensor x, Tensor ref_sorted) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous(), "wdist_sorted: x must be a contiguous (n, F) GPU tensor");
+  const int dt = dt_of(x);
+  const int64_t n = x.size(0), F = x.size(1);
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 20), "wdist_sorted: 1 <= n <= 2^20, got n = ", n);
+  TORCH_CHECK(F >= 1 && F <= 1024, "wdist_sorted: 1 <= F <= 1024, got F = ", F);
+  CHECK_F32(ref_sorted);
+  TORCH_CHECK(ref_sorted.device() == x.device() && ref_sorted.dim() == 2 && ref_sorted.size(0) == F &&
+                  ref_sorted.size(1) == n,
+              "wdist_sorted: ref_sorted must be (F, n) = (", F, ", ", n, ") fp32 on x's device");
+  GUARD(x);
+  const auto f32 = x.options().dtype(at::kFloat), f64 = x.options().dtype(at::kDouble);
+  Tensor out = out_empty({F + 1}, f64);
+  Tensor ws = out_empty({F, n}, f32);  // sorted 32-bit keys
+  Tensor slab = out_empty({F, (int64_t)hfrep::wdist_blocks((int)n)}, f64);
+  hfrep::launch_wdist_sorted(dt, x.data_ptr(), ref_sorted.data_ptr<float>(), reinterpret_cast<uint32_t*>(ws.data_ptr()),
+                             slab.data_ptr<double>(), out.data_ptr<double>(), (int)n, (int)F, cur_stream(x));
+  return out;
+}
+
 // ------------------------------------------------------------------------------------ p2p all-reduce
 // The buffer is a uint8 tensor over the hipExtMallocWithFlags allocation (freed by its deleter);
 // its data_ptr is the allocation base, which is what an IPC handle names.
@@ -1053,6 +1076,7 @@ TORCH_LIBRARY(hfrep, m) {
   m.def("nadam_(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor step, Tensor m_cache, float lr, float b1, float b2, float eps, float gscale) -> ()");
   m.def("step_advance_(Tensor(a!) step, Tensor(b!)? m_cache, float b1) -> ()");
   m.def("clip_(Tensor(a!) p, float c) -> ()");
+  m.def("wdist_sorted(Tensor x, Tensor ref_sorted) -> Tensor");
   m.def("p2p_buffer(int cap, int device) -> Tensor", &p2p_buffer);  // no tensor inputs: catch-all kernel
   m.def("p2p_handle(Tensor buf) -> int[]");
   m.def("p2p_open(int[] handle, int device) -> int", &p2p_open);
@@ -1109,4 +1133,5 @@ TORCH_LIBRARY_IMPL(hfrep, CUDA, m) {
   m.impl("nadam_", &nadam_);
   m.impl("step_advance_", &step_advance_);
   m.impl("clip_", &clip_);
+  m.impl("wdist_sorted", &wdist_sorted);
 }

@@ -206,6 +206,14 @@ void launch_nadam(float* p, const float* g, float* m, float* v, int64_t n, const
 void launch_step_advance(float* step, float* m_cache, float b1, hipStream_t s);
 void launch_clip(float* p, int64_t n, float c, hipStream_t s);
 
+// ---- wdist.hip: per-feature 1-D Wasserstein distance against a pre-sorted reference sample ----
+// x (n, F) fp32 / bf16, ref_sorted (F, n) fp32 ascending rows; out (F + 1) doubles: W1 per feature, then
+// their mean.  ws: F n sorted keys, slab: F wdist_blocks(n) doubles (every element written).
+// 1 <= n <= 2^20, 1 <= F <= 1024 (checked by the binding).  Deterministic (no atomics).
+int wdist_blocks(int n);
+void launch_wdist_sorted(int dt, const void* x, const float* ref_sorted, uint32_t* ws, double* slab, double* out, int n,
+                         int F, hipStream_t s);
+
 // ---- p2p.hip: one-shot all-reduce over IPC-mapped peer buffers (layout in p2p.hip) ----
 constexpr int kP2PMaxRanks = 8, kP2PMaxBlocks = 256;
 constexpr int kP2PCtr = 0, kP2PDone = 128, kP2PErr = 256, kP2PFlags = 4096, kP2PData = 16384;

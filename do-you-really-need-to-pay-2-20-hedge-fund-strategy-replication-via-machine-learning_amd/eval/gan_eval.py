@@ -15,9 +15,11 @@ Differences by design:
 * ``GANEval(..., device='cuda')`` (keyword only) runs the large-N reductions of FID and the MMDs
   on the GPU: the (N*T, F) covariances through the native fp32 weight-gradient kernel (X^T X of the
   centred samples, one fixed-order reduction: deterministic) and the sample means on the device;
-  the F x F matrix square root and the (T x T) Gram matrices stay on the CPU.  It is an fp32 path
-  (relative difference ~1e-6 against the fp64 CPU path, tests/test_kernels_gpu.py); the default
-  CPU path is numerically identical to the reference formulas.
+  the F x F matrix square root and the (T x T) Gram matrices stay on the CPU.  :meth:`wasserstein`
+  sorts ``real`` once with ``torch.sort`` and runs the native sort-and-pair kernel on ``fake``
+  (csrc/wdist.hip; float64 differences and sums of the fp32 inputs).  It is an fp32 path
+  (relative difference ~1e-6 against the fp64 CPU path, tests/test_kernels_gpu.py,
+  tests/test_wdist_gpu.py); the default CPU path is numerically identical to the reference formulas.
 """
 from __future__ import annotations
 
@@ -81,6 +83,18 @@ def _device_moments(a: np.ndarray, device):
     cov = torch.zeros(x.shape[1], x.shape[1], dtype=torch.float32, device=device)
     Fn.linear_wgrad_(xc, xc, cov, None)
     return mu.cpu().numpy(), cov.double().cpu().numpy() / max(x.shape[0] - 1, 1)
+
+
+def _device_wdist(real: np.ndarray, fake: np.ndarray, device) -> np.ndarray:
+    """Per-feature W1 of the (n, F) samples and their mean (F + 1 values) through the native
+    sort-and-pair kernel (csrc/wdist.hip): fp32 inputs, float64 differences and sums; ``real`` is
+    sorted once with ``torch.sort``."""
+    import torch
+
+    from ..ops import functional as Fn
+
+    x, y = (torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=device) for a in (fake, real))
+    return Fn.wdist(x, Fn.wdist_ref(y)).cpu().numpy()
 
 
 class GANEval:
@@ -211,6 +225,9 @@ class GANEval:
         real, fake, _ = self._args(real, fake, dataset)
         assert real.shape == fake.shape and real.ndim in (2, 3)
         real, fake = self._flat(real), self._flat(fake)
+        if self.device is not None:
+            w = _device_wdist(real, fake, self.device)
+            return float(w[-1]) if group else [float(v) for v in w[:-1]]
         res = [wasserstein_distance(real[:, i], fake[:, i]) for i in range(real.shape[1])]
         return float(np.mean(res)) if group else res
 

@@ -326,6 +326,21 @@ def gp_pack(pen: torch.Tensor, weight: float, w: torch.Tensor) -> torch.Tensor:
     return torch.stack([w[0] + w[1] + weight * pen.reshape(()), w[0], w[1], pen.reshape(())])
 
 
+def wdist(x: torch.Tensor, ref_sorted: torch.Tensor) -> torch.Tensor:
+    """(F + 1,) float64: W1 of every column of x (n, F; fp32 / bf16) against the fixed sample whose ascending
+    columns are the rows of ref_sorted (F, n; fp32), then their mean: the W-dist parity metric, stream-ordered
+    on the GPU (csrc/wdist.hip: chunk sort, rank and pair, fixed-order sum; no host synchronise)."""
+    if _nat(x):
+        return _ops().wdist_sorted(x, ref_sorted)
+    return R.wdist_sorted(x, ref_sorted)
+
+
+def wdist_ref(real: torch.Tensor) -> torch.Tensor:
+    """The fixed sample as :func:`wdist` takes it: (F, n) fp32, row f = column f of real (n, F) ascending.
+    A ``torch.sort``, for set-up: the fixed sample is sorted once, outside any loop."""
+    return torch.sort(real.to(torch.float32).t().contiguous(), dim=1).values.contiguous()
+
+
 def interpolate(real: torch.Tensor, fake: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
     """alpha (B,) per-sample: alpha*real + (1-alpha)*fake (GAN/MTSS_WGAN_GP.py:197-199)."""
     if _nat(real):

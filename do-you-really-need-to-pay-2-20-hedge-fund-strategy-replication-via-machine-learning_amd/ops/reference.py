@@ -192,6 +192,16 @@ def gp_coef(g: torch.Tensor, weight: float):
     return pen, v
 
 
+def wdist_sorted(x: torch.Tensor, ref_sorted: torch.Tensor) -> torch.Tensor:
+    """(F + 1,) float64: the 1-D Wasserstein distance of every column of x (n, F) against the sample
+    whose ascending columns are the rows of ref_sorted (F, n), then the mean over the columns.  For
+    equal sample sizes W1 is the mean absolute difference of the order statistics (equal to
+    ``scipy.stats.wasserstein_distance`` per column up to float64 rounding)."""
+    xs = torch.sort(x.to(torch.float64), dim=0).values
+    w = (xs - ref_sorted.to(torch.float64).t()).abs().mean(dim=0)
+    return torch.cat([w, w.mean().reshape(1)])
+
+
 # ======================================================================================
 # 2. explicit primitives (contracts of the native kernels)
 # ======================================================================================

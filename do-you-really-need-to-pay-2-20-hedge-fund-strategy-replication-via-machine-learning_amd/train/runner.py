@@ -16,7 +16,11 @@ prints every iteration and saves the generator once at the very end - a crash lo
   :class:`InjectedFault` after a given iteration - used by the resume tests;
 * optional hipGraph capture of the whole iteration (:class:`GraphedStep`): n_critic critic
   steps + the generator step replay as ONE graph launch, which removes the per-kernel launch
-  cost that dominates at the reference batch of 32.
+  cost that dominates at the reference batch of 32;
+* optional W-dist tracking (``wdist_every`` > 0, :mod:`hfrep.train.wdist_tracker`): the quality metric
+  of a fixed generated sample against held-out real windows, computed on the device between steps
+  and logged through the same deferred snapshots (``w_dist``, ``w_best``, ``w_best_iteration``),
+  with a device-side copy of the best generator so far (``save_best``).
 """
 from __future__ import annotations
 
@@ -53,6 +57,10 @@ class RunOptions:
     fault_at: int | None = None
     fault_rank: int = 0
     graph: bool = False
+    wdist_every: int = 0               # > 0: track the device W-dist every that many iterations (and after the last)
+    wdist_real: object = None          # held-out real windows (N, T, F), or a ready WDistTracker
+    wdist_n: int | None = None         # evaluation windows (default: all of wdist_real; at most 4096)
+    save_best: str | None = None       # write the best-W-dist generator here after the last iteration (rank 0)
 
 
 def _env_fault(opts: RunOptions):
@@ -170,6 +178,25 @@ def _log_tensors(trainer, nan_guard: bool) -> dict:
     return out
 
 
+def _tracker(trainer, opts: RunOptions):
+    """The run's W-dist tracker (None with ``wdist_every == 0``): the one given as ``wdist_real``, or a new
+    one over those windows.  It hangs on the trainer as ``wdist_tracker``, where the training-state
+    checkpoint finds it (utils/checkpoint.py)."""
+    if opts.wdist_every <= 0:
+        trainer.wdist_tracker = None
+        return None
+    from .wdist_tracker import WDistTracker
+
+    if isinstance(opts.wdist_real, WDistTracker):
+        tracker = opts.wdist_real
+    elif opts.wdist_real is None:
+        raise ValueError("wdist_every > 0 needs wdist_real (held-out real windows or a WDistTracker)")
+    else:
+        tracker = WDistTracker(trainer, opts.wdist_real, n=opts.wdist_n)
+    trainer.wdist_tracker = tracker
+    return tracker
+
+
 def resolve_resume(opts: RunOptions, trainer) -> str | None:
     """Checkpoint path to resume from.  Under data parallelism rank 0 resolves it (it is the rank
     that writes checkpoints) and broadcasts the path, so every rank resumes the same iteration even
@@ -235,11 +262,17 @@ def run(trainer, opts: RunOptions, logger: JSONLLogger | None = None) -> list[di
                 raise NonFiniteLoss(f"non-finite loss by iteration {rec['iteration']}")
         d = rec.pop("d", None)
         g = rec.pop("g", None)
+        w = rec.pop("w", None)
         if d is not None:
             rec.update(d_loss=d[0], d_real=d[1], d_fake=d[2], gp=d[3], g_loss=g if not isinstance(g, list) else g[0])
+        if w is not None:
+            if w[2] < 0:  # nothing evaluated yet (the record precedes the first wdist_every-th iteration)
+                w = [None, None, None]
+            rec.update(w_dist=w[0], w_best=w[1], w_best_iteration=w[2] if w[2] is None else int(w[2]))
         records.append(rec)
         logger.log(rec)
 
+    tracker = _tracker(trainer, opts)
     path = resolve_resume(opts, trainer)
     if path:
         resume_state(path, trainer)
@@ -255,13 +288,16 @@ def run(trainer, opts: RunOptions, logger: JSONLLogger | None = None) -> list[di
             if opts.fault_at is not None and it == opts.fault_at and trainer.rank == opts.fault_rank:
                 logger.log({"event": "injected_fault", "iteration": it})
                 raise InjectedFault(f"injected fault after iteration {it} on rank {trainer.rank}")
+            if tracker is not None and (it % opts.wdist_every == 0 or it == opts.epochs):
+                tracker.update(it)  # eager, between graph replays: stream-ordered, no host synchronise
             if it % opts.log_every == 0 or it == opts.epochs:
                 now = time.time()
                 meta = {"iteration": it, "windows_per_s": wpi * (it - it_last) / max(now - t_last, 1e-9)}
                 t_last, it_last = now, it
                 if gs is not None:
                     gs.check_errors()  # non-blocking: raises P2PTimeout once a give-up has reached the host
-                emit(snap.snapshot(meta, **_log_tensors(trainer, opts.nan_guard)))
+                extra = tracker.tensors() if tracker is not None else {}
+                emit(snap.snapshot(meta, **_log_tensors(trainer, opts.nan_guard), **extra))
             if opts.ckpt_dir and opts.ckpt_every and it % opts.ckpt_every == 0:
                 states = _gather_host_rng(trainer)
                 if trainer.rank == 0:
@@ -273,6 +309,8 @@ def run(trainer, opts: RunOptions, logger: JSONLLogger | None = None) -> list[di
         emit(snap.collect())
         if gs is not None:
             gs.check_errors(blocking=True)
+        if tracker is not None and opts.save_best and trainer.rank == 0 and trainer.iteration >= opts.epochs:
+            tracker.save_best(opts.save_best, dict(trainer.cfg.__dict__))
     finally:
         if own_logger:
             logger.close()

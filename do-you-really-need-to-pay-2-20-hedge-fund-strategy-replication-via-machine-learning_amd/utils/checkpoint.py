@@ -122,6 +122,9 @@ def save_training_state(path: str, trainer, rng_states_by_rank=None) -> str:
     }
     st["opt_slots_generator"] = [s.detach().cpu() for s in st["opt_slots_generator"]]
     st["opt_slots_critic"] = [s.detach().cpu() for s in st["opt_slots_critic"]]
+    tracker = getattr(trainer, "wdist_tracker", None)
+    if tracker is not None:  # a run with W-dist tracking on (train/wdist_tracker.py): one extra key
+        st["wdist_tracker"] = tracker.state_dict()
     tmp = path + ".tmp"
     torch.save(st, tmp)
     os.replace(tmp, path)  # atomic: a crash never leaves a truncated checkpoint
@@ -154,4 +157,7 @@ def apply_training_state(st: dict, trainer) -> None:
             gs = by_rank[trainer.rank] if trainer.rank < len(by_rank) else st["rng_gen_state"]
             if gs.numel():
                 trainer.rng.gen.set_state(gs)
+    tracker = getattr(trainer, "wdist_tracker", None)
+    if tracker is not None and "wdist_tracker" in st:
+        tracker.load_state_dict(st["wdist_tracker"])
     trainer.iteration = int(st["iteration"])
