@@ -357,8 +357,10 @@ static void check_head(const optional<Tensor>& d, const optional<Tensor>& w, con
   }
 }
 
+bool lstmf_ahd_supported() { return hfrep::lstmf_ahd_supported(); }
+
 Tensor lstmf_bwd(optional<Tensor> dH, Tensor tape, Tensor U, int64_t act, int64_t B, int64_t Tn, optional<Tensor> hd,
-                 optional<Tensor> hw) {
+                 optional<Tensor> hw, optional<Tensor> ah_out) {
   CHECK_F32(tape);
   const int H = U.size(0);
   check_lstm_U(U, H);
@@ -367,6 +369,12 @@ Tensor lstmf_bwd(optional<Tensor> dH, Tensor tape, Tensor U, int64_t act, int64_
   TORCH_CHECK(hd.has_value() == hw.has_value() && !(hd.has_value() && dH.has_value()),
               "lstmf_bwd: dH or the head factors (hd, hw)");
   check_head(hd, hw, tape, B, Tn * H);
+  if (ah_out.has_value()) {  // extra output: the total adjoint of every h_t, (B, Tn, H)
+    CHECK_F32(*ah_out);
+    TORCH_CHECK(ah_out->numel() == B * Tn * H && ah_out->is_contiguous() && ah_out->device() == tape.device(),
+                "lstmf_bwd: ah_out must be a contiguous (B, T, H) fp32 tensor on the tape's device");
+    TORCH_CHECK(hfrep::lstmf_ahd_supported(), "lstmf_bwd: ah_out needs the split-recurrent BPTT (lstmf_ahd_supported)");
+  }
   GUARD(tape);
   Tensor dZ = out_empty({B, Tn, 4 * H}, tape.options());
   Tensor dHm;
@@ -380,8 +388,39 @@ Tensor lstmf_bwd(optional<Tensor> dH, Tensor tape, Tensor U, int64_t act, int64_
   const float* dhp = dHm.defined() ? dHm.data_ptr<float>() : dH.has_value() ? dH->data_ptr<float>() : nullptr;
   const bool ok = hfrep::launch_lstmf_bwd(dhp, tape.data_ptr<float>(), U.data_ptr<float>(), dZ.data_ptr<float>(), B, Tn,
                                           H, (int)act, cur_stream(tape), head ? hd->data_ptr<float>() : nullptr,
-                                          head ? hw->data_ptr<float>() : nullptr);
+                                          head ? hw->data_ptr<float>() : nullptr,
+                                          ah_out.has_value() ? ah_out->data_ptr<float>() : nullptr);
   TORCH_CHECK(ok, "lstmf_bwd: unsupported H / act");
+  return dZ;
+}
+
+// single-stream tangent reverse (csrc/lstm_f32.hip lstmf_tbwd1_kernel): dZ from the saved h adjoints aH of
+// the tangent seed's BPTT; primal seed dH, or the head factors (hd may be absent: zero seed), or neither
+Tensor lstmf_tbwd1(optional<Tensor> dH, Tensor aH, Tensor tape, Tensor ttape, Tensor U, int64_t act, int64_t B,
+                   int64_t Tn, optional<Tensor> hd, optional<Tensor> hw) {
+  CHECK_F32(tape); CHECK_F32(ttape); CHECK_F32(aH);
+  const int H = U.size(0);
+  check_lstm_U(U, H);
+  TORCH_CHECK(tape.numel() == (int64_t)hfrep::lstmf_tape_elems(B, Tn) && ttape.numel() == tape.numel(), "tape size");
+  TORCH_CHECK(aH.numel() == B * Tn * H && aH.is_contiguous() && aH.device() == tape.device(),
+              "lstmf_tbwd1: aH must be a contiguous (B, T, H) fp32 tensor on the tape's device");
+  if (dH.has_value()) {
+    CHECK_F32(*dH);
+    TORCH_CHECK(dH->numel() == B * Tn * H && dH->is_contiguous() && dH->device() == tape.device(),
+                "lstmf_tbwd1: adjoint shape");
+  }
+  const bool head = hw.has_value();
+  TORCH_CHECK(!head || !dH.has_value(), "lstmf_tbwd1: the adjoint dH or head factors, not both");
+  TORCH_CHECK(head || !hd.has_value(), "lstmf_tbwd1: hd needs hw");
+  check_head(hd, hw, tape, B, Tn * H);
+  GUARD(tape);
+  Tensor dZ = out_empty({B, Tn, 4 * H}, tape.options());
+  const bool ok = hfrep::launch_lstmf_tbwd1(dH.has_value() ? dH->data_ptr<float>() : nullptr, aH.data_ptr<float>(),
+                                            tape.data_ptr<float>(), ttape.data_ptr<float>(), U.data_ptr<float>(),
+                                            dZ.data_ptr<float>(), B, Tn, H, (int)act, cur_stream(tape),
+                                            head && hd.has_value() ? hd->data_ptr<float>() : nullptr,
+                                            head ? hw->data_ptr<float>() : nullptr);
+  TORCH_CHECK(ok, "lstmf_tbwd1: unsupported H / act");
   return dZ;
 }
 
@@ -1040,7 +1079,11 @@ TORCH_LIBRARY(hfrep, m) {
   m.def("lstmf_fwd(Tensor x, Tensor W, Tensor? b, Tensor U, int act, bool save) -> (Tensor, Tensor)");
   m.def("linear_head_cs(Tensor x, Tensor W, Tensor? b, int split, float wa, float wb, Tensor(a!) gW, Tensor(b!)? gb) -> Tensor");
   m.def("linear_head_cs_supported(int K) -> bool", &linear_head_cs_supported);
-  m.def("lstmf_bwd(Tensor? dH, Tensor tape, Tensor U, int act, int B, int T, Tensor? hd=None, Tensor? hw=None) -> Tensor");
+  m.def("lstmf_bwd(Tensor? dH, Tensor tape, Tensor U, int act, int B, int T, Tensor? hd=None, Tensor? hw=None, "
+        "Tensor(a!)? ah_out=None) -> Tensor");  // ah_out: also written, the h adjoints (B, T, H)
+  m.def("lstmf_ahd_supported() -> bool", &lstmf_ahd_supported);  // no tensor inputs: catch-all kernel
+  m.def("lstmf_tbwd1(Tensor? dH, Tensor aH, Tensor tape, Tensor ttape, Tensor U, int act, int B, int T, Tensor? hd=None, "
+        "Tensor? hw=None) -> Tensor");
   m.def("lstmf_tbwd(Tensor? dH, Tensor? dHd, Tensor tape, Tensor ttape, Tensor U, int act, int B, int T, Tensor? hd=None, "
         "Tensor? hdd=None, Tensor? hw=None) -> (Tensor, Tensor)");
   m.def("lstmf_tfwd(Tensor xd, Tensor W, Tensor U, Tensor tape, int act) -> (Tensor, Tensor)");
@@ -1102,6 +1145,7 @@ TORCH_LIBRARY_IMPL(hfrep, CUDA, m) {
   m.impl("linear_head_cs", &linear_head_cs);
   m.impl("lstmf_bwd", &lstmf_bwd);
   m.impl("lstmf_tbwd", &lstmf_tbwd);
+  m.impl("lstmf_tbwd1", &lstmf_tbwd1);
   m.impl("lstmf_dgrad", &lstmf_dgrad);
   m.impl("fp3_split", &fp3_split);
   m.impl("fp3_join", &fp3_join);

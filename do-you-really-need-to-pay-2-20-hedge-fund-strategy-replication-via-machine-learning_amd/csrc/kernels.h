@@ -52,8 +52,17 @@ bool launch_lstmf_tfwd(const float* xd, const float* W, const float* U, const fl
 // hd / hw (HEAD): dH = hd (x) hw generated in the kernel (the critic head's adjoint: hd (B), hw (Tn H));
 // dH is then unused.  Not with the exact-fp32 BPTT (lstmf_head_supported() false: materialise dH).
 bool launch_lstmf_bwd(const float* dH, const float* tape, const float* U, float* dZ, int B, int Tn, int H, int act,
-                      hipStream_t s, const float* hd = nullptr, const float* hw = nullptr);
+                      hipStream_t s, const float* hd = nullptr, const float* hw = nullptr, float* aH = nullptr);
 bool lstmf_head_supported();
+// aH (B,T,H): the BPTT also stores the total adjoint of every h_t (dH_t + dz_{t+1} U^T), which the
+// single-stream tangent reverse reads.  Split-recurrent BPTT only (lstmf_ahd_supported() false: exact mode).
+bool lstmf_ahd_supported();
+// single-stream tangent reverse: dZ of lstm_seq_tbwd when the tangent seed's own BPTT has run and left
+// its h adjoints aH (= a_hd per step); dH or the head factors (hd, hw) are the primal seed, both may be
+// null (hw alone: HEAD addressing with a zero seed)
+bool launch_lstmf_tbwd1(const float* dH, const float* aH, const float* tape, const float* ttape, const float* U, float* dZ,
+                        int B, int Tn, int H, int act, hipStream_t s, const float* hd = nullptr,
+                        const float* hw = nullptr);
 // hw (HEAD): dH = hd (x) hw, dHd = hdd (x) hw generated in the kernel (a null factor: that adjoint is 0)
 bool launch_lstmf_tbwd(const float* dH, const float* dHd, const float* tape, const float* ttape, const float* U, float* dZ,
                        float* dZd, int B, int Tn, int H, int act, hipStream_t s, const float* hd = nullptr,

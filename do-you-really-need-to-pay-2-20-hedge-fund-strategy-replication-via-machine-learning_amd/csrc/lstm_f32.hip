@@ -901,6 +901,228 @@ lstmf_tbwdp_kernel(const float* __restrict__ dH, const float* __restrict__ dHd, 
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// single-stream tangent reverse: lstmf_tbwd1_kernel
+// ------------------------------------------------------------------------------------------
+// The tangent system is the linearisation of the primal one, so the adjoint of every tangent quantity
+// (a_hd, a_cd, dzd) depends on no tangent value: it is the plain BPTT of the tangent seed dHd.  When that
+// BPTT has already run (the gradient penalty: the BPTT on x_hat seeded with ones, then the tangent reverse
+// seeded with ones), its per-step total h adjoint aH (lstmf_bwds_kernel<.., AHD>) is this kernel's a_hd and
+// its dZ is the dZd operand of the weight gradient: here only the primal adjoint stream runs
+// (ops/reference.py lstm_seq_tbwd_ahd).  a_cd follows from a_hd by the elementwise carry
+// a_cd = acd_n + a_hd o d1, acd_n = a_cd f.  lstmf_tbwdp_kernel's layout minus the second stream: the MFMA
+// role issues 200 exact-fp32 MFMAs per half-phase (dz U^T only) and stores dZ, the cell role carries three
+// values per cell and half (c, cdot via the tapes, the two carries) and one set of step loads (gates, zdot,
+// c_{t-1}, cdot_{t-1}, dH, aH).  dH / the head factor hd may be null (no primal seed).
+#ifndef HFREP_TBWD1_CELLGROUP
+#define HFREP_TBWD1_CELLGROUP 2  // cells per schedule region of the cell role, as in lstmf_tbwdp_kernel
+#endif
+#ifndef HFREP_TBWD1_EARLYLOAD
+#define HFREP_TBWD1_EARLYLOAD 1  // 0: the cell role's loads after the last cell of a half (A/B: docs/PERF.md)
+#endif
+template <int ACT, bool HEAD = false>
+__global__ void __launch_bounds__(512, 1)
+lstmf_tbwd1_kernel(const float* __restrict__ dH, const float* __restrict__ aH, const float* __restrict__ tape,
+                   const float* __restrict__ ttape, const float* __restrict__ U, float* __restrict__ dZ, int B, int Tn,
+                   const float* __restrict__ hd, const float* __restrict__ hw) {
+  extern __shared__ __attribute__((aligned(16))) float fsm[];
+  float* zt = fsm;                   // dz tile  [32][BZ_LR]
+  float* ht = zt + 32 * BZ_LR;       // dz U^T   [32][BH_LR]
+  float* trash = ht + 32 * BH_LR;    // [4 * BZ_KQ] padding-cell writes
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int w = wv & 3;
+  const int q = lane & 3, g = lane >> 4, j4 = (lane & 15) >> 2, c16 = lane & 15;
+  const int nrb = (B + 31) / 32;
+  if (wv < 4) {
+    // ---------------- MFMA role ----------------
+    float ut[2][FH];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int j = 16 * (2 * w + e) + c16;
+      const bool ok = j < FH;
+#pragma unroll
+      for (int k = 0; k < FH; ++k) {
+        const float v = U[(ok ? j : 0) * FG + g * FH + k];
+        ut[e][k] = ok ? v : 0.f;
+      }
+    }
+    // rows of half M of dz U^T -> the dh tile
+    auto half_a = [&](auto MA_) {
+      constexpr int M = decltype(MA_)::value;
+      f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+      const float* ar = zt + (16 * M + c16) * BZ_LR + g * BZ_KQ;
+#pragma unroll
+      for (int jj = 0; jj < FH / 4; ++jj) {
+        const f32x4 a4 = *reinterpret_cast<const f32x4*>(ar + 4 * jj);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          acc[0] = mma4(a4[s], ut[0][4 * jj + s], acc[0]);
+          acc[1] = mma4(a4[s], ut[1][4 * jj + s], acc[1]);
+        }
+        if ((jj & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int col = 16 * (2 * w + e) + c16;
+        if (2 * w + e < 7) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) ht[(16 * M + 4 * g + i) * BH_LR + col] = acc[e][i];
+        }
+      }
+    };
+    // the dz stores ride on the MFMA role: threads 0..199 own chunk tid % 100 of rows 2 k + tid / 100; a
+    // half's rows are stable for exactly the half-phase after the one that completed them
+    const int srr = tid / 100, sch = tid - 100 * srr, sqq = sch / 25, sc = sch - 25 * sqq;
+    const int slo = (srr & 1) * BZ_LR + sqq * BZ_KQ + 4 * sc;
+    const int sgo = tid < 200 ? (srr * Tn * FG + sqq * FH + 4 * sc) * 4 : kOOB;
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+      const int row0 = rb * 32;
+      const rsrc_t rz = ftile_rsrc(dZ, row0, B, Tn, FG);
+      const int nr = min(32, B - row0);
+      auto store_half = [&](auto M_, int ts) {
+        constexpr int M = decltype(M_)::value;
+#pragma unroll
+        for (int k = 8 * M; k < 8 * M + 8; ++k) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(zt + slo + 2 * k * BZ_LR);
+          st16(v, rz, 2 * k + srr < nr, sgo, (2 * k * Tn + ts) * FG * 4);
+          if (k & 1) __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      for (int i = tid; i < 32 * (BZ_LR + BH_LR); i += 512) zt[i] = 0.f;  // both tiles
+      __syncthreads();
+      for (int t = Tn - 1; t >= 0; --t) {
+        if (t < Tn - 1) store_half(I1{}, t + 1);  // rows 16..31 of dz_{t+1}: stable during P1(t)
+        half_a(I1{});
+        lds_barrier();
+        store_half(I0{}, t);                      // rows 0..15 of dz_t: stable during P2(t)
+        half_a(I0{});
+        lds_barrier();
+      }
+      store_half(I1{}, 0);
+      __syncthreads();
+    }
+  } else {
+    // ---------------- cell role ----------------
+    const int ub = FUW * w + j4;
+    const int hr = (4 * g + q) * BH_LR + ub, zw = (4 * g + q) * BZ_LR + ub;
+    const int tl = ftape_lane(w, lane), tcl = ftape_cell(w, lane);
+    for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+      const int row0 = rb * 32;
+      const rsrc_t rdh = ftile_rsrc(dH, row0, B, Tn, FH), rah = ftile_rsrc(aH, row0, B, Tn, FH);
+      const rsrc_t rt = ftape_rsrc(tape, rb, nrb, Tn), rtt = ftape_rsrc(ttape, rb, nrb, Tn);
+      int vp1[2];
+#pragma unroll
+      for (int m = 0; m < 2; ++m) vp1[m] = ((16 * m + 4 * g + q) * Tn * FH + ub) * 4;
+      // HEAD: dH = hd (x) w generated per cell (a null factor: the primal seed is zero)
+      float hdv[2] = {0.f, 0.f};
+      const rsrc_t rhw = make_rsrc(hw, HEAD ? Tn * FH * 4 : 0);
+      if constexpr (HEAD) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          const int r = row0 + 16 * m + 4 * g + q;
+          hdv[m] = (hd && r < B) ? hd[r] : 0.f;
+        }
+      }
+      const int hvo = ub * 4;
+      float tc[2][FNT], tcd[2][FNT], acn[2][FNT], acdn[2][FNT];
+      f32x4 tg[FNT], tz[FNT];
+      float tcp[FNT], tcdp[FNT], tdh[FNT], tah[FNT];
+      // the step loads of (half M, cell n) at step tt (one register set, reused by the two halves in turn).
+      // The per-lane part of every address is one of four VGPRs (tl, tcl, vp1[m]); the cell's slot
+      // and the step go into the uniform soffset, so no per-cell offset registers are hoisted
+      // (out-of-range lanes: voffset kOOB, which the range check drops whatever the soffset)
+      auto load_cell = [&](auto M_, int n, int tt, bool on) {
+        constexpr int m = decltype(M_)::value;
+        const int tp = tt > 0 ? tt - 1 : 0;
+        const bool tok = on && !(w == 3 && n >= 4);
+        const int sg = tt * FT_STEP * 4 + ftape_slot(m, n), sc = tp * FT_STEP * 4 + ftape_slot(m, n);
+        const int sd = tt * FH * 4 + 16 * n;
+        tg[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rt, tok ? tl : kOOB, sg, 0));
+        tz[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rtt, tok ? tl : kOOB, sg, 0));
+        tcp[n] = ld1(rt, (tok && tt > 0) ? tcl : kOOB, sc);
+        tcdp[n] = ld1(rtt, (tok && tt > 0) ? tcl : kOOB, sc);
+        if constexpr (HEAD) tdh[n] = hdv[m] * ld1(rhw, tok ? hvo : kOOB, sd);
+        else tdh[n] = ld1(rdh, tok ? vp1[m] : kOOB, sd);
+        tah[n] = ld1(rah, tok ? vp1[m] : kOOB, sd);
+      };
+      auto load_half = [&](auto M_, int tt, bool on) {
+#pragma unroll
+        for (int n = 0; n < FNT; ++n) load_cell(M_, n, tt, on);
+      };
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < FNT; ++n) {
+          const bool tok = !(w == 3 && n >= 4);
+          const int oc = tcl + (Tn - 1) * FT_STEP * 4 + ftape_slot(m, n);
+          acn[m][n] = 0.f;
+          acdn[m][n] = 0.f;
+          tc[m][n] = ld1(rt, tok ? oc : kOOB, 0);
+          tcd[m][n] = ld1(rtt, tok ? oc : kOOB, 0);
+        }
+      load_half(std::integral_constant<int, 0>{}, Tn - 1, true);
+      for (int i = tid; i < 32 * (BZ_LR + BH_LR); i += 512) zt[i] = 0.f;
+      __syncthreads();
+      // cells of half M.  Each cell issues the loads of the set's next use (half MN at step tn) right after its
+      // own math, as lstmf_bwds_kernel's cells do: with half the matrix work the cell role waits on its loads,
+      // not on the MFMA role (HFREP_TBWD1_EARLYLOAD=0: all seven after the last cell, lstmf_tbwdp_kernel's order,
+      // +6 % per call; a second register set for the 16-byte loads spills: docs/PERF.md)
+      auto half_b = [&](auto M_, auto MN_, int tn, bool non) {
+        constexpr int m = decltype(M_)::value;
+#pragma unroll
+        for (int n = 0; n < FNT; ++n) {
+          const bool tok = !(w == 3 && n >= 4);
+          const float i_ = tg[n][0], f_ = tg[n][1], g_ = tg[n][2], o_ = tg[n][3];
+          const float zdi = tz[n][0], zdf = tz[n][1], zdg = tz[n][2], zdo = tz[n][3];
+          const float c = tc[m][n], cd = tcd[m][n], cp = tcp[n], cdp = tcdp[n];
+          const float si = i_ * (1.f - i_), sf = f_ * (1.f - f_), so = o_ * (1.f - o_), sg = act_dy(ACT, g_);
+          const float idot = si * zdi, fdot = sf * zdf, gdot = sg * zdg, odot = so * zdo;
+          const float ca = act_f(ACT, c), d1 = act_dy(ACT, ca), d2 = act_d2y(ACT, ca);
+          const float a_h = tdh[n] + ht[hr + 16 * m * BH_LR + 4 * n], a_hd = tah[n];
+          const float a_od = a_hd * ca;
+          const float a_o = a_h * ca + a_hd * d1 * cd;
+          const float a_cd = acdn[m][n] + a_hd * o_ * d1;
+          const float a_c = acn[m][n] + a_h * o_ * d1 + a_hd * (odot * d1 + o_ * d2 * cd);
+          const float a_fd = a_cd * cp, a_id = a_cd * g_, a_gd = a_cd * i_;
+          const float a_f = a_c * cp + a_cd * cdp;
+          const float a_i = a_c * g_ + a_cd * gdot;
+          const float a_g = a_c * i_ + a_cd * idot;
+          acn[m][n] = tok ? a_c * f_ + a_cd * fdot : 0.f;
+          acdn[m][n] = tok ? a_cd * f_ : 0.f;
+          const float s2i = si * (1.f - 2.f * i_), s2f = sf * (1.f - 2.f * f_), s2o = so * (1.f - 2.f * o_);
+          const float s2g = act_d2y(ACT, g_);
+          float z4[4];
+          z4[0] = a_i * si + a_id * s2i * zdi;
+          z4[1] = a_f * sf + a_fd * s2f * zdf;
+          z4[2] = a_g * sg + a_gd * s2g * zdg;
+          z4[3] = a_o * so + a_od * s2o * zdo;
+          float* zp = tok ? zt + zw + 16 * m * BZ_LR + 4 * n : trash;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) zp[k * BZ_KQ] = z4[k];
+          tc[m][n] = cp;
+          tcd[m][n] = cdp;
+          if constexpr (HFREP_TBWD1_EARLYLOAD) load_cell(MN_, n, tn, non);
+          if ((n + 1) % HFREP_TBWD1_CELLGROUP == 0 || n == FNT - 1) __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (!HFREP_TBWD1_EARLYLOAD) load_half(MN_, tn, non);
+      };
+      using I0 = std::integral_constant<int, 0>;
+      using I1 = std::integral_constant<int, 1>;
+      for (int t = Tn - 1; t >= 0; --t) {
+        half_b(I0{}, I1{}, t, true);                        // P1(t): B(0, t), then half 1's loads for P2(t)
+        lds_barrier();
+        half_b(I1{}, I0{}, t > 0 ? t - 1 : 0, t > 0);       // P2(t): B(1, t), then half 0's loads for P1(t - 1)
+        lds_barrier();
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // ==========================================================================================
 // fused fp32 LSTM weight gradients
 // ==========================================================================================
@@ -2039,13 +2261,18 @@ lstmf_fwds_kernel(const float* __restrict__ x, const float* __restrict__ W, cons
 // word per plane), row stride 424 (conflict-free ds_read_b128).  B[k][j] = U[j][(k & 3) H + (k >> 2)],
 // k >= 400 zero: 312 registers per wave, 252 of them pinned in AGPRs.  One tape register set: a cell's
 // loads for the other half's next use are issued as soon as it has consumed the set.
+// AHD: the total adjoint of every h_t (dht = dH_t + dz_{t+1} U^T) also leaves as a row-major (B, T, H)
+// tensor aH: the single-stream tangent reverse (lstmf_tbwd1_kernel) reads it as its tangent-stream
+// adjoint.  One dword store per cell behind the cell's next tape loads, addressed like the cell's dH load
+// (lane row in voffset, step and unit tile in soffset); dZ is bitwise the AHD = false kernel's.
 constexpr int BS_LZ = 432;             // dz plane row stride (bf16 elements): 216 dwords
 constexpr int BS_PL = 32 * BS_LZ * 2;  // bytes per dz plane (32 rows)
 
-template <int ACT, bool HEAD = false>
+template <int ACT, bool HEAD = false, bool AHD = false>
 __global__ void __launch_bounds__(256, 1)
 lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, const float* __restrict__ U,
-                  float* __restrict__ dZ, int B, int Tn, const float* __restrict__ hd, const float* __restrict__ hw) {
+                  float* __restrict__ dZ, int B, int Tn, const float* __restrict__ hd, const float* __restrict__ hw,
+                  float* __restrict__ aH) {
   extern __shared__ __attribute__((aligned(16))) float fsm[];
   float* zt = fsm;                                     // fp32 dz tile [32][BZ_LR]: [q][u'] per row
   float* ht = zt + 32 * BZ_LR;                         // dh_rec tile [32][BH_LR]
@@ -2096,6 +2323,7 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
     const int row0 = rb * 32;
     const rsrc_t rdh = ftile_rsrc(dH, row0, B, Tn, FH), rt = ftape_rsrc(tape, rb, nrb, Tn);
     const rsrc_t rz = ftile_rsrc(dZ, row0, B, Tn, FG);
+    const rsrc_t rah = ftile_rsrc(AHD ? aH : nullptr, row0, B, Tn, FH);
     const int nr = min(32, B - row0);
     int vp1[2];
 #pragma unroll
@@ -2177,6 +2405,8 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
                                max(tp - 1, 0) * FT_STEP * 4 + ftape_slot(0, n), tp * FH * 4 + 16 * n, tok && t > 0,
                                tp > 0, hdv[0], rhw, hvo);
       }
+      // (rows past B: voffset past the descriptor; padding cells: kOOB)
+      if constexpr (AHD) st1(dht, rah, tok ? vp1[m] : kOOB, t * FH * 4 + 16 * n);
     };
     // one half-phase: dz rows of half MA out to HBM, the cells of half 1 - MA at step t, and rows MA of
     // dh_rec = dz[rows MA] U^T (the planes hold dz_{t + 1} there for MA = 1, dz_t for MA = 0)
@@ -2641,7 +2871,7 @@ static std::atomic<int>& bwdf_impl() {
 }
 template <int ACT>
 void bwdf_launch(const float* dH, const float* tape, const float* U, float* dZ, int B, int Tn, hipStream_t s,
-                 const float* hd, const float* hw) {
+                 const float* hd, const float* hw, float* aH) {
   const int ver = bwdf_impl().load(std::memory_order_relaxed);
   const int nrb = (B + 31) / 32, cus = device_cu_count();
   const size_t sm = (size_t)(32 * BZ_LR + 32 * BH_LR + 4 * BZ_KQ) * 4;
@@ -2649,12 +2879,18 @@ void bwdf_launch(const float* dH, const float* tape, const float* U, float* dZ, 
     auto go = [&](auto k) {
       allow_lds(reinterpret_cast<const void*>(k));
       hipLaunchKernelGGL(k, dim3(nrb < cus ? nrb : cus), dim3(256), sm + 16 + 3 * BS_PL, s, dH, tape, U, dZ, B, Tn, hd,
-                         hw);
+                         hw, aH);
     };
-    if (hd) go(lstmf_bwds_kernel<ACT, true>);
-    else go(lstmf_bwds_kernel<ACT, false>);
+    if (aH) {
+      if (hd) go(lstmf_bwds_kernel<ACT, true, true>);
+      else go(lstmf_bwds_kernel<ACT, false, true>);
+    } else {
+      if (hd) go(lstmf_bwds_kernel<ACT, true>);
+      else go(lstmf_bwds_kernel<ACT, false>);
+    }
     return;
   }
+  if (aH) throw std::runtime_error("lstmf_bwd: the exact-fp32 BPTT does not store the h adjoints (lstmf_ahd_supported)");
   if (hd) throw std::runtime_error("lstmf_bwd: the exact-fp32 BPTT takes a materialised dH (lstmf_head_supported)");
   auto k = lstmf_bwdp_kernel<ACT>;
   allow_lds(reinterpret_cast<const void*>(k));
@@ -2663,13 +2899,14 @@ void bwdf_launch(const float* dH, const float* tape, const float* U, float* dZ, 
 static_assert((32 * BZ_LR + 32 * BH_LR + 4 * BZ_KQ) * 4 + 16 + 3 * BS_PL <= F_LDS_MAX, "split BPTT LDS");
 int set_lstmf_bwd_impl(int v) { return bwdf_impl().exchange(v); }
 bool lstmf_head_supported() { return bwdf_impl().load(std::memory_order_relaxed) != 2; }
+bool lstmf_ahd_supported() { return bwdf_impl().load(std::memory_order_relaxed) != 2; }
 bool launch_lstmf_bwd(const float* dH, const float* tape, const float* U, float* dZ, int B, int Tn, int H, int act,
-                      hipStream_t s, const float* hd, const float* hw) {
+                      hipStream_t s, const float* hd, const float* hw, float* aH) {
   if (H != FH || B <= 0 || Tn <= 0) return false;
   switch (act) {
-    case ACT_LINEAR: bwdf_launch<ACT_LINEAR>(dH, tape, U, dZ, B, Tn, s, hd, hw); return true;
-    case ACT_SIGMOID: bwdf_launch<ACT_SIGMOID>(dH, tape, U, dZ, B, Tn, s, hd, hw); return true;
-    case ACT_TANH: bwdf_launch<ACT_TANH>(dH, tape, U, dZ, B, Tn, s, hd, hw); return true;
+    case ACT_LINEAR: bwdf_launch<ACT_LINEAR>(dH, tape, U, dZ, B, Tn, s, hd, hw, aH); return true;
+    case ACT_SIGMOID: bwdf_launch<ACT_SIGMOID>(dH, tape, U, dZ, B, Tn, s, hd, hw, aH); return true;
+    case ACT_TANH: bwdf_launch<ACT_TANH>(dH, tape, U, dZ, B, Tn, s, hd, hw, aH); return true;
     default: return false;
   }
 }
@@ -2696,6 +2933,29 @@ bool launch_lstmf_tbwd(const float* dH, const float* dHd, const float* tape, con
     case ACT_LINEAR: tbwdf_launch<ACT_LINEAR>(dH, dHd, tape, ttape, U, dZ, dZd, B, Tn, s, hd, hdd, hw); return true;
     case ACT_SIGMOID: tbwdf_launch<ACT_SIGMOID>(dH, dHd, tape, ttape, U, dZ, dZd, B, Tn, s, hd, hdd, hw); return true;
     case ACT_TANH: tbwdf_launch<ACT_TANH>(dH, dHd, tape, ttape, U, dZ, dZd, B, Tn, s, hd, hdd, hw); return true;
+    default: return false;
+  }
+}
+template <int ACT>
+void tbwd1f_launch(const float* dH, const float* aH, const float* tape, const float* ttape, const float* U, float* dZ,
+                   int B, int Tn, hipStream_t s, const float* hd, const float* hw) {
+  const int cus = device_cu_count();
+  const size_t sm = (size_t)(32 * BZ_LR + 32 * BH_LR + 4 * BZ_KQ) * 4;
+  const int nrb = (B + 31) / 32;
+  auto go = [&](auto k) {
+    allow_lds(reinterpret_cast<const void*>(k));
+    hipLaunchKernelGGL(k, dim3(nrb < cus ? nrb : cus), dim3(512), sm, s, dH, aH, tape, ttape, U, dZ, B, Tn, hd, hw);
+  };
+  if (hw) go(lstmf_tbwd1_kernel<ACT, true>);
+  else go(lstmf_tbwd1_kernel<ACT, false>);
+}
+bool launch_lstmf_tbwd1(const float* dH, const float* aH, const float* tape, const float* ttape, const float* U, float* dZ,
+                        int B, int Tn, int H, int act, hipStream_t s, const float* hd, const float* hw) {
+  if (H != FH || B <= 0 || Tn <= 0 || !aH) return false;
+  switch (act) {
+    case ACT_LINEAR: tbwd1f_launch<ACT_LINEAR>(dH, aH, tape, ttape, U, dZ, B, Tn, s, hd, hw); return true;
+    case ACT_SIGMOID: tbwd1f_launch<ACT_SIGMOID>(dH, aH, tape, ttape, U, dZ, B, Tn, s, hd, hw); return true;
+    case ACT_TANH: tbwd1f_launch<ACT_TANH>(dH, aH, tape, ttape, U, dZ, B, Tn, s, hd, hw); return true;
     default: return false;
   }
 }

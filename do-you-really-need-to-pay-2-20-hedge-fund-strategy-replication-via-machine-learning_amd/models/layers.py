@@ -99,7 +99,9 @@ class Layer:
     def etfwd(self, ctx, xd):
         raise NotImplementedError
 
-    def etbwd(self, ctx, tctx, dy, dyd, need_dx: bool):
+    # ``need_dxd=False``: the caller has the tangent adjoints already (Sequential.etbwd with a ``btape``) and
+    # drops dxd; a layer skips computing it where that is a launch of its own
+    def etbwd(self, ctx, tctx, dy, dyd, need_dx: bool, need_dxd: bool = True):
         raise NotImplementedError
 
     def w(self, name):
@@ -167,7 +169,7 @@ class Dense(Layer):
         yd = Fn.act_backward(zd, ctx["y"], self.act_code)  # act'(z) * zdot
         return yd, {"xd": xd, "zd": zd}
 
-    def etbwd(self, ctx, tctx, dy, dyd, need_dx):
+    def etbwd(self, ctx, tctx, dy, dyd, need_dx, need_dxd=True):
         dzd = Fn.act_backward(dyd, ctx["y"], self.act_code)
         # dy is None (no primal seed) with a piecewise-linear activation: dz == 0 (f'' = 0), so its weight
         # gradient term vanishes and dx is the zero adjoint (None) -- nothing is materialised
@@ -178,7 +180,7 @@ class Dense(Layer):
         Fn.run_wgrad(Fn.linear_wgrad_, tctx["xd"], dzd, self.g("kernel"), None)
         if not need_dx:
             return None, None
-        return (None if zero_dz else self._dgrad(dz)), self._dgrad(dzd)
+        return (None if zero_dz else self._dgrad(dz)), (self._dgrad(dzd) if need_dxd else None)
 
 
 class LSTM(Layer):
@@ -209,9 +211,21 @@ class LSTM(Layer):
                                      save)
         return hs, ({"x": x, "hs": hs, "tape": tape} if save else None)
 
-    def ebwd(self, ctx, dy, need_dx, wgrad=True):
+    def ebwd(self, ctx, dy, need_dx, wgrad=True, keep=None):
+        """``keep`` (a dict): also record this BPTT's dZ and per-step h adjoints (``"dZ"``, ``"ahd"``) for a
+        single-stream tangent reverse at the same tape, where the path supports it."""
         U = self.p("recurrent_kernel")
         dx = None
+        if keep is not None:
+            got = Fn.lstm_layer_bwd_keep(dy, ctx["tape"], U, self.act_code, W=self.p("kernel") if need_dx else None)
+            if got is not None:
+                dZ, dx, keep["ahd"] = got
+                keep["dZ"] = dZ
+                keep["dy"] = None  # (only the two-stream fallback reads it: not held from here to the tangent reverse)
+                if wgrad:
+                    Fn.run_wgrad(Fn.lstm_wgrad_, ctx["x"], ctx["hs"], dZ, self.g("kernel"), self.g("recurrent_kernel"),
+                                 self.g("bias"))
+                return dx
         if need_dx:  # dX = dZ W^T comes out of the BPTT launch itself; dZ is only kept for wgrad
             dZ, dx = Fn.lstm_layer_bwd(dy, ctx["tape"], U, self.act_code, W=self.p("kernel"), need_dz=wgrad)
         else:
@@ -224,12 +238,22 @@ class LSTM(Layer):
         hds, ttape = Fn.lstm_layer_tfwd(xd, self.p("kernel"), ctx["tape"], self.p("recurrent_kernel"), self.act_code)
         return hds, {"xd": xd, "hds": hds, "ttape": ttape}
 
-    def etbwd(self, ctx, tctx, dy, dyd, need_dx):
+    def etbwd(self, ctx, tctx, dy, dyd, need_dx, need_dxd=True, brec=None):
+        """``brec``: this layer's record of ``ebwd(..., keep=...)`` at the same tape with the seed the tangent
+        output has here: its dZ is this pass's dZd and its h adjoints feed the single-stream kernel."""
         U = self.p("recurrent_kernel")
         dx = dxd = None
-        if need_dx:
+        if brec is not None and "ahd" in brec:
+            # (the record is consumed here: popped, so its tensors go back to the allocator in stream order as soon
+            # as their last reader is launched -- the weight gradient's operands are held by Fn.run_wgrad)
+            dZd, ahd = brec.pop("dZ"), brec.pop("ahd")
+            dZ = Fn.lstm_layer_tbwd1(dy, ahd, ctx["tape"], tctx["ttape"], U, self.act_code)
+            del ahd
+            if need_dx:
+                dx = Fn.linear_dgrad(dZ, self.p("kernel"))
+        elif need_dx:
             dZ, dZd, dx, dxd = Fn.lstm_layer_tbwd(dy, dyd, ctx["tape"], tctx["ttape"], U, self.act_code,
-                                                  W=self.p("kernel"))
+                                                  W=self.p("kernel"), need_dxd=need_dxd)
         else:
             dZ, dZd = Fn.lstm_layer_tbwd(dy, dyd, ctx["tape"], tctx["ttape"], U, self.act_code)
         Fn.run_wgrad(Fn.lstm_wgrad_, ctx["x"], ctx["hs"], dZ, self.g("kernel"), self.g("recurrent_kernel"), self.g("bias"),
@@ -267,7 +291,7 @@ class LayerNormalization(Layer):
     def etfwd(self, ctx, xd):
         return Fn.layer_norm_tfwd(xd, ctx["xhat"], ctx["rstd"], self.p("gamma")), {"xd": xd}
 
-    def etbwd(self, ctx, tctx, dy, dyd, need_dx):
+    def etbwd(self, ctx, tctx, dy, dyd, need_dx, need_dxd=True):
         return Fn.layer_norm_tbwd_(dy, dyd, tctx["xd"], ctx["xhat"], ctx["rstd"], self.p("gamma"), self.g("gamma"),
                                    self.g("beta"), need_dx)
 
@@ -295,11 +319,11 @@ class LeakyReLU(Layer):
     def etfwd(self, ctx, xd):
         return Fn.act_backward(xd, ctx["y"], 3), {}
 
-    def etbwd(self, ctx, tctx, dy, dyd, need_dx):
+    def etbwd(self, ctx, tctx, dy, dyd, need_dx, need_dxd=True):
         if not need_dx:
             return None, None
         dx = Fn.act_backward(dy, ctx["y"], 3) if dy is not None else None
-        return dx, Fn.act_backward(dyd, ctx["y"], 3)
+        return dx, (Fn.act_backward(dyd, ctx["y"], 3) if need_dxd else None)
 
 
 class Flatten(Layer):
@@ -322,7 +346,7 @@ class Flatten(Layer):
     def etfwd(self, ctx, xd):
         return xd.reshape(xd.shape[0], -1), {}
 
-    def etbwd(self, ctx, tctx, dy, dyd, need_dx):
+    def etbwd(self, ctx, tctx, dy, dyd, need_dx, need_dxd=True):
         if not need_dx:
             return None, None
         return (dy.reshape(ctx["shape"]) if dy is not None else None), dyd.reshape(ctx["shape"])
@@ -374,7 +398,7 @@ class Conv1D(Layer):
         zd = Fn.linear(cols_d, self.p("kernel").reshape(-1, self.filters), None, 0)
         return Fn.act_backward(zd, ctx["y"], self.act_code), {"cols_d": cols_d, "zd": zd}
 
-    def etbwd(self, ctx, tctx, dy, dyd, need_dx):
+    def etbwd(self, ctx, tctx, dy, dyd, need_dx, need_dxd=True):
         Wk = self.p("kernel").reshape(-1, self.filters)
         gk = self.g("kernel").reshape(-1, self.filters)
         if dy is None:
@@ -386,7 +410,7 @@ class Conv1D(Layer):
         if not need_dx:
             return None, None
         return (Fn.col2im_causal(Fn.linear_dgrad(dz, Wk), self.k, self.dil, self.cin),
-                Fn.col2im_causal(Fn.linear_dgrad(dzd, Wk), self.k, self.dil, self.cin))
+                Fn.col2im_causal(Fn.linear_dgrad(dzd, Wk), self.k, self.dil, self.cin) if need_dxd else None)
 
 
 def _init_tensor(spec: ParamSpec, gen, layer: Layer) -> torch.Tensor:
@@ -558,15 +582,25 @@ class Sequential(torch.nn.Module):
             return dy.materialize()
         return dy
 
-    def ebwd(self, tape, dy, need_dx: bool = False, wgrad: bool = True, hook=None):
-        """Reverse pass; ``hook(i)`` runs after layer i (its gradients are then final)."""
+    def ebwd(self, tape, dy, need_dx: bool = False, wgrad: bool = True, hook=None, keep: bool = False):
+        """Reverse pass; ``hook(i)`` runs after layer i (its gradients are then final).  ``keep=True``: returns
+        ``(dx, btape)``, btape[i] holding the adjoint layer i received (``"dy"``) and, for LSTM layers on a path
+        with the single-stream tangent reverse, the BPTT's ``"dZ"`` and h adjoints ``"ahd"``: what
+        ``etbwd(..., btape=btape)`` reuses when its tangent seed is this pass's seed."""
+        btape = [None] * len(self.layers)
         for i in range(len(self.layers) - 1, -1, -1):
             need = need_dx or i > 0
             layer = self.layers[i]
-            dy = layer.ebwd(tape[i], self._adj(layer, dy), need, wgrad)
+            dy = self._adj(layer, dy)
+            if keep:
+                btape[i] = {"dy": dy}
+                dy = layer.ebwd(tape[i], dy, need, wgrad, keep=btape[i]) if isinstance(layer, LSTM) else \
+                    layer.ebwd(tape[i], dy, need, wgrad)
+            else:
+                dy = layer.ebwd(tape[i], dy, need, wgrad)
             if hook is not None:
                 hook(i)
-        return Fn._mat(dy)
+        return (Fn._mat(dy), btape) if keep else Fn._mat(dy)
 
     def etfwd(self, tape, xd, head_out: bool = True):
         """``head_out=False``: the tangent of a linear Dense head is not evaluated (placeholder), as in
@@ -582,11 +616,22 @@ class Sequential(torch.nn.Module):
             ttape.append(tctx)
         return xd, ttape
 
-    def etbwd(self, tape, ttape, dy, dyd, need_dx: bool = False, hook=None):
+    def etbwd(self, tape, ttape, dy, dyd, need_dx: bool = False, hook=None, btape=None):
+        """``btape``: the record of ``ebwd(tape, dyd, ..., keep=True)`` -- the plain reverse pass at the same
+        tape with the same seed as this pass's tangent seed.  The tangent system is the linearisation of the
+        primal one, so the adjoint of every tangent quantity is that pass's adjoint of the matching primal
+        quantity: each layer takes its tangent adjoint from the record, no layer computes dxd (the returned
+        dxd is None), and an LSTM layer with recorded dZ / h adjoints runs the single-stream kernel."""
         for i in range(len(self.layers) - 1, -1, -1):
             need = need_dx or i > 0
             layer = self.layers[i]
-            dy, dyd = layer.etbwd(tape[i], ttape[i], self._adj(layer, dy), self._adj(layer, dyd), need)
+            if btape is not None:
+                rec = btape[i]
+                kw = {"brec": rec} if isinstance(layer, LSTM) else {}
+                dy, _ = layer.etbwd(tape[i], ttape[i], self._adj(layer, dy), rec["dy"], need, need_dxd=False, **kw)
+                dyd = btape[i] = rec = None  # (a record is used once)
+            else:
+                dy, dyd = layer.etbwd(tape[i], ttape[i], self._adj(layer, dy), self._adj(layer, dyd), need)
             if hook is not None:
                 hook(i)
         return Fn._mat(dy), Fn._mat(dyd)

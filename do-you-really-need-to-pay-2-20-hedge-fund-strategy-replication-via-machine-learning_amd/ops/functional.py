@@ -457,6 +457,49 @@ def lstm_layer_bwd(dH, tape, U, act: int, W=None, need_dz: bool = True):
     return dZ if W is None else (dZ, linear_dgrad(dZ, W))
 
 
+def lstm_layer_bwd_keep(dH, tape, U, act: int, W=None):
+    """:func:`lstm_layer_bwd` that also hands out the total adjoint of every h_t (``a_hd``, (B, T, H):
+    dH_t + dz_{t+1} U^T) for a later single-stream tangent reverse (:func:`lstm_layer_tbwd1`): returns
+    ``(dZ, dX or None, a_hd)``, or None where the path has no support (bf16, generic widths, the
+    exact-fp32 BPTT): the caller then runs the plain :func:`lstm_layer_bwd`."""
+    if isinstance(tape, FTape):
+        if not _ops().lstmf_ahd_supported():
+            return None
+        ah = torch.empty((tape.B, tape.T, U.shape[0]), dtype=torch.float32, device=tape.t.device)
+        if isinstance(dH, OuterAdjoint) and dH.d.dtype == torch.float32:
+            dZ = _ops().lstmf_bwd(None, tape.t, U, int(act), tape.B, tape.T, dH.d.contiguous(),
+                                  dH.w.reshape(-1).contiguous(), ah)
+        else:
+            dH = _mat(dH)
+            dZ = _ops().lstmf_bwd(None if dH is None else dH.contiguous(), tape.t, U, int(act), tape.B, tape.T, None,
+                                  None, ah)
+        return dZ, (None if W is None else linear_dgrad(dZ, W)), ah
+    if isinstance(tape, torch.Tensor) or _nat(tape[0]):
+        return None
+    gates, cs = tape
+    dZ, ah = R.lstm_seq_bwd_ahd(_mat(dH), gates, cs, U.to(gates.dtype), act)
+    return dZ, (None if W is None else linear_dgrad(dZ, W)), ah
+
+
+def lstm_layer_tbwd1(dH, a_hd, tape, ttape, U, act: int, W=None):
+    """dZ of the reverse-over-tangent pass from the saved ``a_hd`` of the tangent seed's own BPTT
+    (:func:`lstm_layer_bwd_keep` on the same tape; that BPTT's dZ is this pass's dZd); ``dH``: the primal
+    seed (a tensor, a lazy head adjoint or None).  With ``W`` returns ``(dZ, dX)``."""
+    if isinstance(tape, FTape):
+        if isinstance(dH, OuterAdjoint) and dH.d.dtype == torch.float32:
+            dZ = _ops().lstmf_tbwd1(None, a_hd, tape.t, ttape.t, U, int(act), tape.B, tape.T, dH.d.contiguous(),
+                                    dH.w.reshape(-1).contiguous())
+        else:
+            dH = _mat(dH)
+            dZ = _ops().lstmf_tbwd1(None if dH is None else dH.contiguous(), a_hd, tape.t, ttape.t, U, int(act), tape.B,
+                                    tape.T)
+    else:
+        gates, cs = tape
+        zds, cds = ttape
+        dZ = R.lstm_seq_tbwd_ahd(_mat(dH), a_hd, gates, cs, zds, cds, U.to(gates.dtype), act)
+    return dZ if W is None else (dZ, linear_dgrad(dZ, W))
+
+
 def lstm_layer_tfwd(xd, W, tape, U, act: int):
     if isinstance(tape, FTape):
         hds, ttape = _ops().lstmf_tfwd(xd.contiguous(), W, U, tape.t, int(act))
@@ -494,8 +537,9 @@ def lstm_wgrad_(x, hs, dZ, gW, gU, gb, xd=None, hds=None, dZd=None, impl: int = 
         linear_wgrad_(hds, dZd, gU, None, shift_T=T)
 
 
-def lstm_layer_tbwd(dH, dHd, tape, ttape, U, act: int, W=None):
-    """(dZ, dZd) of the reverse-over-tangent pass; with ``W`` also (dX, dXd) = (dZ W^T, dZd W^T)."""
+def lstm_layer_tbwd(dH, dHd, tape, ttape, U, act: int, W=None, need_dxd: bool = True):
+    """(dZ, dZd) of the reverse-over-tangent pass; with ``W`` also (dX, dXd) = (dZ W^T, dZd W^T).
+    ``need_dxd=False``: dXd is not wanted (None where it would be a GEMM of its own)."""
     if isinstance(tape, FTape):
         heads = [a for a in (dH, dHd) if isinstance(a, OuterAdjoint)]
         if heads and all(a is None or (isinstance(a, OuterAdjoint) and a.w is heads[0].w and a.d.dtype == torch.float32)
@@ -507,7 +551,7 @@ def lstm_layer_tbwd(dH, dHd, tape, ttape, U, act: int, W=None):
             dH, dHd = _mat(dH), _mat(dHd)
             dZ, dZd = _ops().lstmf_tbwd(None if dH is None else dH.contiguous(), None if dHd is None else dHd.contiguous(),
                                         tape.t, ttape.t, U, int(act), tape.B, tape.T)
-        return (dZ, dZd) if W is None else (dZ, dZd, linear_dgrad(dZ, W), linear_dgrad(dZd, W))
+        return (dZ, dZd) if W is None else (dZ, dZd, linear_dgrad(dZ, W), linear_dgrad(dZd, W) if need_dxd else None)
     if isinstance(tape, torch.Tensor):
         heads = [a for a in (dH, dHd) if isinstance(a, OuterAdjoint)]
         Wk = W if _lstm2_dx_fused(W) else None
@@ -525,7 +569,7 @@ def lstm_layer_tbwd(dH, dHd, tape, ttape, U, act: int, W=None):
             dZ, dZd, dX, dXd = _ops().lstm2_tbwd(None if dH is None else dH.contiguous(), dHd.contiguous(), tape,
                                                  ttape, U, int(act), Wk)
         if W is not None and Wk is None:
-            dX, dXd = linear_dgrad(dZ, W), linear_dgrad(dZd, W)
+            dX, dXd = linear_dgrad(dZ, W), linear_dgrad(dZd, W) if need_dxd else None
         return (dZ, dZd) if W is None else (dZ, dZd, dX, dXd)
     dH, dHd = _mat(dH), _mat(dHd)
     gates, cs = tape
@@ -533,4 +577,4 @@ def lstm_layer_tbwd(dH, dHd, tape, ttape, U, act: int, W=None):
     if dH is None:
         dH = torch.zeros_like(dHd)
     dZ, dZd = lstm_seq_tbwd(dH, dHd, gates, cs, zds, cds, U, act)
-    return (dZ, dZd) if W is None else (dZ, dZd, linear_dgrad(dZ, W), linear_dgrad(dZd, W))
+    return (dZ, dZd) if W is None else (dZ, dZd, linear_dgrad(dZ, W), linear_dgrad(dZd, W) if need_dxd else None)

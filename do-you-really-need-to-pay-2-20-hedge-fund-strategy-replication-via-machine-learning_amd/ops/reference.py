@@ -257,6 +257,33 @@ def lstm_seq_bwd(dh_seq: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor, U:
     return dz_all
 
 
+def lstm_seq_bwd_ahd(dh_seq: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor, U: torch.Tensor, act: int):
+    """:func:`lstm_seq_bwd` that also returns the total adjoint of every h_t, ``dht = dh_seq[:, t] +
+    dz_{t+1} U^T`` (B,T,H): (dZ, a_hd).  Contract of the native ``lstmf_bwd`` op's ``ah_out``."""
+    B, T, G = gates.shape
+    H = G // 4
+    dz_all = torch.empty_like(gates)
+    ah_all = torch.empty_like(cs)
+    dh = dh_seq.new_zeros(B, H)
+    dc = dh_seq.new_zeros(B, H)
+    Ut = U.t()
+    for t in range(T - 1, -1, -1):
+        i, f, g, o = gates[:, t].split(H, dim=1)
+        c = cs[:, t]
+        cp = cs[:, t - 1] if t > 0 else torch.zeros_like(c)
+        ca = apply_act(c, act)
+        dht = dh_seq[:, t] + dh
+        ah_all[:, t] = dht
+        do = dht * ca
+        dct = dc + dht * o * act_dy(ca, act)
+        di, dg, df = dct * g, dct * i, dct * cp
+        dc = dct * f
+        dz = torch.cat([di * i * (1 - i), df * f * (1 - f), dg * act_dy(g, act), do * o * (1 - o)], dim=1)
+        dz_all[:, t] = dz
+        dh = dz @ Ut
+    return dz_all, ah_all
+
+
 def lstm_seq_tfwd(dzx: torch.Tensor, gates: torch.Tensor, cs: torch.Tensor, U: torch.Tensor, act: int):
     """Tangent (JVP) of the recurrence at a saved primal point.
 
@@ -342,6 +369,54 @@ def lstm_seq_tbwd(dh_seq, dhd_seq, gates, cs, zds, cds, U, act: int):
         ah_n = dz @ Ut
         ahd_n = dzd @ Ut
     return dZ, dZd
+
+
+def lstm_seq_tbwd_ahd(dh_seq, ahd_seq, gates, cs, zds, cds, U, act: int):
+    """Single-stream reverse pass of the tangent system: the dZ of :func:`lstm_seq_tbwd` when the total
+    adjoint of every tangent output, ``a_hd[:, t] = dhd_seq[:, t] + dzd_{t+1} U^T``, is given.
+
+    The tangent system is linear in the tangent values, so its adjoints (a_hd, a_cd, dzd) are the plain
+    BPTT of ``dhd_seq`` (:func:`lstm_seq_bwd_ahd` returns exactly ``dzd`` and ``a_hd``): only the primal
+    adjoint stream is left, with ``a_cd`` from the elementwise carry.  ``dh_seq`` None = zero seed.
+    Contract of the native ``lstmf_tbwd1`` op.
+    """
+    B, T, G = gates.shape
+    H = G // 4
+    dZ = torch.empty_like(gates)
+    ah_n = gates.new_zeros(B, H)
+    ac_n = gates.new_zeros(B, H)
+    acd_n = gates.new_zeros(B, H)
+    Ut = U.t()
+    for t in range(T - 1, -1, -1):
+        i, f, g, o = gates[:, t].split(H, dim=1)
+        c = cs[:, t]
+        cd = cds[:, t]
+        cp = cs[:, t - 1] if t > 0 else torch.zeros_like(c)
+        cdp = cds[:, t - 1] if t > 0 else torch.zeros_like(c)
+        zdi, zdf, zdg, zdo = zds[:, t].split(H, dim=1)
+        si, sf, so = i * (1 - i), f * (1 - f), o * (1 - o)
+        sg = act_dy(g, act)
+        idot, fdot, gdot, odot = si * zdi, sf * zdf, sg * zdg, so * zdo
+        ca = apply_act(c, act)
+        d1 = act_dy(ca, act)
+        d2 = act_d2y(ca, act)
+        a_h = ah_n if dh_seq is None else dh_seq[:, t] + ah_n
+        a_hd = ahd_seq[:, t]
+        a_od = a_hd * ca
+        a_o = a_h * ca + a_hd * d1 * cd
+        a_cd = acd_n + a_hd * o * d1
+        a_c = ac_n + a_h * o * d1 + a_hd * (odot * d1 + o * d2 * cd)
+        a_fd, a_id, a_gd = a_cd * cp, a_cd * g, a_cd * i
+        a_f = a_c * cp + a_cd * cdp
+        a_i = a_c * g + a_cd * gdot
+        a_g = a_c * i + a_cd * idot
+        ac_n = a_c * f + a_cd * fdot
+        acd_n = a_cd * f
+        dz = torch.cat([a_i * si + a_id * si * (1 - 2 * i) * zdi, a_f * sf + a_fd * sf * (1 - 2 * f) * zdf,
+                        a_g * sg + a_gd * act_d2y(g, act) * zdg, a_o * so + a_od * so * (1 - 2 * o) * zdo], dim=1)
+        dZ[:, t] = dz
+        ah_n = dz @ Ut
+    return dZ
 
 
 def shift_prev(h_seq: torch.Tensor) -> torch.Tensor:

@@ -272,18 +272,40 @@ class GANTrainer:
         if xrf is None:
             xrf = torch.cat([real, fake], 0)
         side = self._side(0)
+        # the x_hat BPTT and the tangent reverse are both seeded with ones, so the tangent adjoints of the
+        # latter are the adjoints of the former (docs/ARCHITECTURE.md, "adjoint reuse"): the BPTT keeps them
+        # (btape) and the tangent reverse runs its primal stream only.  HFREP_GP_REUSE=0: the two-stream pass.
+        reuse = os.environ.get("HFREP_GP_REUSE", "1") != "0"
+        btape = None
+
+        def input_grad(sh, tape_h):
+            ones = self._ones(sh)
+            if not reuse:
+                return C.ebwd(tape_h, ones, need_dx=True, wgrad=False), None
+            return C.ebwd(tape_h, ones, need_dx=True, wgrad=False, keep=True)
+
+        def second_order(sd, tape_h, ttape, btape, hook):
+            ones = self._ones(sd)
+            if btape is not None:  # the precondition: the record is of the BPTT seeded with this very (cached) tensor
+                assert ones is btape[-1]["dy"], "adjoint reuse needs the same ones seed on both passes"
+            C.etbwd(tape_h, ttape, None, ones, hook=hook, btape=btape)
+
         if side is not None:
             # the gradient penalty's input-gradient chain (forward on x_hat, backward with wgrad off) and
             # the tangent forward along v = dGP/dg write no gradient and share nothing with the W-terms
             # chain: they run on a side stream; only the tangent reverse (whose weight gradient
             # accumulates into C.flat.grad after the W terms') waits for the join.  Every tensor the side
             # chain allocates lives until after the join, and the side stream's next use starts with a
-            # fork from this stream, so no allocator block is reused across the streams while in use.
+            # fork from this stream, so no allocator block is reused across the streams while in use.  That
+            # covers the BPTT's record (btape: dZ and the h adjoints of both LSTM layers, allocated on the
+            # side stream): the tangent reverse and the weight-gradient stream read it after the join; each
+            # layer's record is dropped once its readers are launched (Fn.run_wgrad holds a deferred weight
+            # gradient's operands until its own join), so its blocks wait in the side stream's pool.
             cur = torch.cuda.current_stream(self.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side), trange("critic/gp_input_grad"):
                 sh, tape_h = C.efwd(xh, save=True, head_out=False)  # D(x_hat) itself is never read
-                g = C.ebwd(tape_h, self._ones(sh), need_dx=True, wgrad=False)
+                g, btape = input_grad(sh, tape_h)
                 pen, v = Fn.gp_coef(g, self.gp_weight)
                 sd, ttape = C.etfwd(tape_h, v.to(xh.dtype), head_out=False)
         hook = self._hook(C)
@@ -300,6 +322,9 @@ class GANTrainer:
                 # both segment means and the score gradient in one launch
                 w, ds = Fn.gan_loss(s, s.numel() // 2, -1.0, 1.0, 0)
                 C.ebwd(tape, ds)
+                # (the W terms' tape is dead from here: released before the penalty's passes allocate theirs;
+                # what a deferred weight gradient still reads is held by Fn.run_wgrad until the join)
+                del tape, s, ds
             if side is not None:
                 cur.wait_stream(side)
             # gradient penalty: g = dD/dx_hat (input gradient only), v = dGP/dg, then the
@@ -307,14 +332,14 @@ class GANTrainer:
             if side is None:
                 with trange("critic/gp_input_grad"):
                     sh, tape_h = C.efwd(xh, save=True, head_out=False)  # D(x_hat) itself is never read
-                    g = C.ebwd(tape_h, self._ones(sh), need_dx=True, wgrad=False)
+                    g, btape = input_grad(sh, tape_h)
                     pack, v = Fn.gp_coef_pack(g, self.gp_weight, w)  # [total, W real, W fake, GP]
                 with trange("critic/gp_second_order"):
                     sd, ttape = C.etfwd(tape_h, v.to(xh.dtype), head_out=False)
             else:
                 pack = Fn.gp_pack(pen, self.gp_weight, w)
             with trange("critic/gp_second_order"):
-                C.etbwd(tape_h, ttape, None, self._ones(sd), hook=hook)
+                second_order(sd, tape_h, ttape, btape, hook)
         return pack.to(self._acc)
 
     def _ones(self, like):
