@@ -64,7 +64,8 @@ def _dataset(data: str, n: int, window: int, features: int, seed: int, rank: int
 
 def _add_train_args(p):
     p.add_argument("--model", default="mtss_wgan_gp",
-                   help="gan | wgan | wgan_gp | mtss_gan | mtss_wgan | mtss_wgan_gp | conv_wgan_gp, or a legacy "
+                   help="gan | wgan | wgan_gp | mtss_gan | mtss_wgan | mtss_wgan_gp | conv_wgan_gp | ln_wgan_gp | "
+                        "mtss_ln_wgan_gp, or a legacy "
                         "class name (GAN, WGAN, MTTS_WGAN_GP, MTTS_GAN, MTTS_WGAN, WGAN_GP)")
     p.add_argument("--preset", default="reference", choices=sorted(PRESETS))
     for k in ("window", "features", "batch_size", "epochs", "n_windows", "seed", "log_every"):

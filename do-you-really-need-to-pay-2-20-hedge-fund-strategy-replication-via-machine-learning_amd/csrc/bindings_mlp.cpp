@@ -397,6 +397,56 @@ std::tuple<Tensor, Tensor> mlp_wgan_critic_dx(Tensor x, std::vector<Tensor> cp) 
   return {dx, slab};
 }
 
+// ---- that critic under the gradient penalty ((mlp_ln, wgan_gp)): outputs through the poison allocator ----
+// first-order pass on x_hat: xg (2, B, T, F) = [x_hat; g], g = ds/dx_hat, and gsq (B, T) fp32 = |g_r|^2 per row
+// (-> mlp_wgp_coef); xg is the X operand of gW1's one streaming product (see mlp_lngp_critic)
+std::tuple<Tensor, Tensor> mlp_lngp_norm(Tensor x, std::vector<Tensor> cp) {
+  const int dt = act_dt(x);
+  const int64_t F = x.size(-1), H = hidden_of(cp, F), M = rows_of(x, F, "x");
+  const auto cr = clip_of(cp, F, H);
+  TORCH_CHECK(M > 0, "mlp_lngp_norm: empty batch");
+  GUARD(x);
+  Tensor xg = hfrep::out_empty({2, x.size(0), x.size(1), F}, x.options());
+  Tensor gsq = hfrep::out_empty({x.size(0), x.size(1)}, x.options().dtype(at::kFloat));
+  hfrep::launch_mlp_lngp_norm(dt, x.data_ptr(), cr, xg[0].data_ptr(), xg[1].data_ptr(), gsq.data_ptr<float>(), M, (int)F,
+                              (int)H, cur_stream(x));
+  return {xg, gsq};
+}
+
+// the penalty's reverse over the tangent along v = c_b g, xg = [x_hat; g] from mlp_lngp_norm: adds the two
+// gammas', beta1's, the head's and the two Dense biases' gradients into cg (fixed-order slab sums; beta2 and b3
+// get nothing) and returns the weight-gradient operands as row-stacked (2, B, T, H) pairs
+//   U = [u1; u1d], DZ2 = [dz2; dzt2], DZ1 = [dz1; dzt1]:  gW2 += U^T DZ2,  gW1 += xg^T DZ1
+// (linear_wgrad_ over the 2 M rows, without its bias column: that would add the tangent rows)
+std::tuple<Tensor, Tensor, Tensor> mlp_lngp_critic(Tensor xg, Tensor c, std::vector<Tensor> cp,
+                                                   std::vector<Tensor> cg) {
+  const int dt = act_dt(xg);
+  TORCH_CHECK(xg.dim() == 4 && xg.size(0) == 2, "mlp_lngp_critic: xg must be (2, B, T, F)");
+  const Tensor x = xg[0], g = xg[1];
+  const int64_t F = x.size(-1), H = hidden_of(cp, F), M = rows_of(x, F, "x"), B = x.size(0), T = x.size(1);
+  const auto cr = clip_of(cp, F, H);
+  TORCH_CHECK(M > 0, "mlp_lngp_critic: empty batch");
+  TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kFloat && c.is_contiguous() && c.numel() == B &&
+                  c.device() == x.device(),
+              "mlp_lngp_critic: c (B) fp32");
+  TORCH_CHECK(cg.size() == 10, "mlp_lngp_critic: 10 gradient views");
+  const int64_t n[10] = {F * H, H, H, H, H * H, H, H, H, H, 1};
+  float* p[10];
+  for (int i = 0; i < 10; ++i) {
+    TORCH_CHECK(cg[i].device() == x.device(), "mlp_lngp_critic: gradients on the activations' device");
+    p[i] = const_cast<float*>(w(cg[i], n[i], "critic gradient"));
+  }
+  GUARD(x);
+  Tensor o[3];
+  for (auto& t : o) t = hfrep::out_empty({2, B, T, H}, x.options());
+  Tensor lnslab = slab_new_p(x, M, hfrep::mlp_lngp_slab_cols((int)H));
+  hfrep::launch_mlp_lngp_critic(dt, x.data_ptr(), g.data_ptr(), c.data_ptr<float>(), cr, o[0][0].data_ptr(),
+                                o[0][1].data_ptr(), o[1][0].data_ptr(), o[1][1].data_ptr(), o[2][0].data_ptr(),
+                                o[2][1].data_ptr(), lnslab.data_ptr<float>(), p[2], p[3], p[6], p[8], p[1], p[5], M,
+                                (int)T, (int)F, (int)H, cur_stream(x));
+  return {o[0], o[1], o[2]};
+}
+
 Tensor mlp_finish(Tensor slab, optional<Tensor> e, int64_t mode, double invB, optional<Tensor> b3, double lam) {
   TORCH_CHECK(slab.is_cuda() && slab.scalar_type() == at::kFloat && slab.is_contiguous() && slab.dim() == 2 &&
                   slab.size(1) == 2,
@@ -452,6 +502,8 @@ TORCH_LIBRARY_FRAGMENT(hfrep, m) {
   m.def("mlp_gan_critic(Tensor x, Tensor[] cp, float label) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("mlp_wgan_critic(Tensor x, Tensor[] cp, float label, Tensor(a!)[] cg) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mlp_wgan_critic_dx(Tensor x, Tensor[] cp) -> (Tensor, Tensor)");
+  m.def("mlp_lngp_norm(Tensor x, Tensor[] cp) -> (Tensor, Tensor)");
+  m.def("mlp_lngp_critic(Tensor xg, Tensor c, Tensor[] cp, Tensor(a!)[] cg) -> (Tensor, Tensor, Tensor)");
   m.def("mlp_gen_bwd(Tensor noise, Tensor dfake, Tensor[] gp) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("mlp_finish(Tensor slab, Tensor? e, int mode, float invB, Tensor? b3, float lam) -> Tensor");
   m.def("mlp_slab_sum_(Tensor slab, int L, Tensor(a!)? o0, Tensor(b!)? o1=None, Tensor(c!)? o2=None, "
@@ -474,6 +526,8 @@ TORCH_LIBRARY_IMPL(hfrep, CUDA, m) {
   m.impl("mlp_gen_bwd", &mlp_gen_bwd);
   m.impl("mlp_wgan_critic", &mlp_wgan_critic);
   m.impl("mlp_wgan_critic_dx", &mlp_wgan_critic_dx);
+  m.impl("mlp_lngp_norm", &mlp_lngp_norm);
+  m.impl("mlp_lngp_critic", &mlp_lngp_critic);
   m.impl("mlp_finish", &mlp_finish);
   m.impl("mlp_slab_sum_", &mlp_slab_sum_);
 }

@@ -1,5 +1,6 @@
 // Fused MLP-GAN passes (csrc/mlp.hip): host launchers for BASELINE configs 3 / 4 (the vanilla GAN of
-// GAN/GAN.py and the MLP WGAN-GP of GAN/WGAN_GP.py) and the clipped MLP WGAN of GAN/WGAN.py.  Included
+// GAN/GAN.py and the MLP WGAN-GP of GAN/WGAN_GP.py), the clipped MLP WGAN of GAN/WGAN.py and its critic under
+// the gradient penalty.  Included
 // only by mlp.hip and bindings_mlp.cpp.
 //
 // Every launcher takes the fp32 master weights (Keras layout: kernel (in, out), row-major) and
@@ -68,6 +69,20 @@ void launch_mlp_wgan_critic(int dt, const void* x, const MlpClip& cr, float labe
 // the generator step's input gradient through that critic: dx = d mean(-s) / dx; slab (2: sum of -s_r | 0)
 void launch_mlp_wgan_critic_dx(int dt, const void* x, const MlpClip& cr, void* dx, float* slab, int64_t M, int F,
                                int H, hipStream_t s);
+// The same critic under the gradient penalty (model (mlp_ln, wgan_gp)).  lngp_norm: g = ds/dx of every row
+// (M, F; dtype dt), xc = a copy of x (the row block in front of g in one buffer) and gsq (M) fp32 = the
+// squared norm of g per row (launch_mlp_wgp_coef sums a sample's T rows).
+// lngp_critic: the reverse over the tangent along v_r = c_b g_r (c: per sample, rows = B Tn) as wgrad
+// operands u1, u1d (X of W2), dz2, dzt2 (dY of W2), dz1, dzt1 (dY of W1; X = x and g: dzt1 carries c_b);
+// lnslab (mlp_slab_rows(M) x mlp_lngp_slab_cols(H) scratch, every row written): the per-wave column sums
+// dgamma1 | dbeta1 | dgamma2 | gw3 | gb1 | gb2, added in a fixed order into gg1 ... gb2.
+void launch_mlp_lngp_norm(int dt, const void* x, const MlpClip& cr, void* xc, void* g, float* gsq, int64_t M, int F,
+                          int H, hipStream_t s);
+int mlp_lngp_slab_cols(int H);
+void launch_mlp_lngp_critic(int dt, const void* x, const void* g, const float* c, const MlpClip& cr, void* u1,
+                            void* u1d, void* dz2, void* dzt2, void* dz1, void* dzt1, float* lnslab, float* gg1,
+                            float* gbe1, float* gg2, float* gw3, float* gb1, float* gb2, int64_t M, int Tn, int F, int H,
+                            hipStream_t s);
 // fixed-order reduction of a loss slab (P rows x 2) and optional per-sample e (n_e values) into
 // out[4]: mode 0 = WGAN-GP critic pack [w_real + w_fake + lam pen, w_real, w_fake, pen];
 // mode 1 = generator loss [loss, 0, 0, 0] (W: -mean score; BCE: mean); mode 2 = mean of the per-row losses

@@ -31,6 +31,10 @@
 // (linear Dense layers, per-row Dense(1) head, no Flatten), so its two passes compose the same blocks:
 // mlp_wgan_critic (one critic update on one batch with its label: wgrad operands u1 / dz2 / dz1, LayerNorm
 // and head gradients as per-wave column-sum slabs) and mlp_wgan_critic_dx (the generator step's dfake).
+//
+// The same critic trained with the gradient penalty (zoo (mlp_ln, wgan_gp)) is not affine, so its penalty is a
+// per-row second-order pass: mlp_lngp_norm (g = ds/dx_hat and its squared norm per row) and mlp_lngp_critic
+// (tangent forward along v = c_b g, then the reverse over primal and tangent through both LayerNorms).
 #include "common.h"
 #include "kernels.h"
 #include "mfma.h"
@@ -2020,6 +2024,418 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_wgan_critic_dx_kernel(const T
 }
 
 // ===================================================================================================
+// the LReLU + LayerNorm critic under the gradient penalty (model (mlp_ln, wgan_gp)): the W terms are two
+// mlp_wgan_critic launches; the penalty adds a first-order pass (mlp_lngp_norm) and the reverse over the
+// tangent (mlp_lngp_critic).  Per row, with phi = LReLU, m = phi'(z), xh = (phi(z) - mean) rstd:
+//   z1 = x W1 + b1, u1 = gamma1 xh1 + beta1, z2 = u1 W2 + b2, u2 = gamma2 xh2 + beta2, s = u2 . w3 + b3
+// ===================================================================================================
+// First-order pass: g = ds/dx_hat of every row (mlp_wgan_critic_dx with ds = 1) and its squared norm,
+// summed from the fp32 registers before g is rounded to T.  gsq is per row: a sample's T rows may lie in
+// different waves and workgroups; mlp_wgp_coef sums them.  xc: a copy of x (the row block in front of g in
+// one (2 M, F) buffer, so that [x_hat; g] is one weight-gradient operand; see mlp_lngp_critic).
+template <typename T, int F, int H>
+__global__ void __launch_bounds__(MLP_THREADS) mlp_lngp_norm_kernel(const T* __restrict__ x, MlpClip c,
+                                                                    T* __restrict__ xc, T* __restrict__ g,
+                                                                    float* __restrict__ gsq, int64_t M) {
+  using Fr = typename MP<T>::frag;
+  constexpr int NTH = (H + 31) / 32, NTF = (F + 31) / 32;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  Fr* f1 = reinterpret_cast<Fr*>(lds);
+  Fr* f2 = f1 + fwd_entries<T, F, H>() * 64;
+  Fr* d2 = f2 + fwd_entries<T, H, H>() * 64;
+  Fr* d1 = d2 + dgrad_entries<T, H, H>() * 64;
+  float* vec = reinterpret_cast<float*>(d1 + dgrad_entries<T, F, H>() * 64);
+  build_fwd<T, F, H>(f1, c.W1);
+  build_fwd<T, H, H>(f2, c.W2);
+  build_dgrad<T, H, H>(d2, c.W2);
+  build_dgrad<T, F, H>(d1, c.W1);
+  load_vec(vec + 0 * VEC, c.b1, H); load_vec(vec + 1 * VEC, c.g1, H); load_vec(vec + 2 * VEC, c.be1, H);
+  load_vec(vec + 3 * VEC, c.b2, H); load_vec(vec + 4 * VEC, c.g2, H); load_vec(vec + 5 * VEC, c.be2, H);
+  load_vec(vec + 6 * VEC, c.w3, H);
+  __syncthreads();
+  const float* gam1 = vec + 1 * VEC;
+  const float* gam2 = vec + 4 * VEC;
+  MLP_LOOP {
+    const int64_t row = tile * 32 + (lane & 31);
+    const bool ok = row < M;
+    f32x16 xr[NTF], a[NTH], y2[NTH], d[NTH];
+    float mean1, rstd1, mean2, rstd2;
+    load_rows<T, F>(xr, x, row, M, h);
+    store_rows<T, F>(xc, row, M, xr, h);
+    clip_forward<T, F, H, false>(xr, a, y2, f1, f2, vec, static_cast<T*>(nullptr), row, M, lane, h, mean1, rstd1, mean2,
+                                 rstd2);
+    head_rows<H>(d, vec + 6 * VEC, 1.f, ok, h);  // du2 = w3
+    ln_reverse<H, ACT_LINEAR, false>(d, y2, d, gam2, mean2, rstd2, h, lane, nullptr);
+    dense<T, H, H>(d, y2, d2, lane);  // du1
+    load_rows<T, F>(xr, x, row, M, h);  // (reloaded, not held across the reverse: register budget)
+    dense<T, F, H>(xr, a, f1, lane);
+    bias_act<H>(a, vec + 0 * VEC, ACT_LINEAR, h);  // y1
+    ln_reverse<H, ACT_LINEAR, false>(y2, a, a, gam1, mean1, rstd1, h, lane, nullptr);
+    dense<T, H, F>(a, xr, d1, lane);  // g
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < NTF; ++t)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) s = fmaf(xr[t][q], xr[t][q], s);
+    s += __shfl_xor(s, 32, 64);
+    if (ok && h == 0) gsq[row] = s;
+    store_rows<T, F>(g, row, M, xr, h);
+  }
+}
+
+// An LDS vector re-read at every use: the per-feature vectors never change after the prologue, so without
+// this every read of gamma / beta / bias / w3 in the tile loop is recognised as loop invariant and hoisted
+// (7 vectors x 64 registers per lane), which spills in the kernel that already holds four H-vectors.
+template <typename V>
+__device__ __forceinline__ const V* reread(const V* p) {
+  int z = 0;
+  asm volatile("" : "+v"(z));
+  return p + z;
+}
+// row statistics of LayerNorm(LReLU(z)) without forming its output (z: Dense outputs, zeros past N)
+template <int N>
+__device__ __forceinline__ void lrelu_stats(const f32x16* z, int h, float& mean, float& rstd) {
+  constexpr int NT = (N + 31) / 32;
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += lrelu(z[t][q]);
+  s += __shfl_xor(s, 32, 64);
+  mean = s * (1.f / N);
+  float v = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const float d = 32 * t + featq(q, h) < N ? lrelu(z[t][q]) - mean : 0.f;
+      v = fmaf(d, d, v);
+    }
+  v += __shfl_xor(v, 32, 64);
+  rstd = 1.f / sqrtf(v * (1.f / N) + LN_EPS_F);
+}
+
+// LReLU + LayerNorm tangent of one row, in place: zd = the Dense tangent z' on entry and
+//   u' = gamma rstd (a' - mean(a') - xh mean(xh a')),  a' = m z'
+// on exit (the closed form of misc.hip layernorm_tfwd_kernel); z: the Dense outputs, (mean, rstd) of lrelu(z).
+template <int N>
+__device__ __forceinline__ void ln_tangent(const f32x16* z, f32x16* zd, const float* gam, float mean, float rstd,
+                                           int h) {
+  constexpr int NT = (N + 31) / 32;
+  const float* gh = gam + 4 * h;
+  float sa = 0.f, sx = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const bool in = 32 * t + featq(q, h) < N;
+      const float zv = z[t][q];
+      const float xh = in ? (lrelu(zv) - mean) * rstd : 0.f;
+      const float ad = in ? (zv >= 0.f ? 1.f : LRELU_ALPHA_F) * zd[t][q] : 0.f;
+      zd[t][q] = ad;
+      sa += ad;
+      sx = fmaf(xh, ad, sx);
+    }
+  sa += __shfl_xor(sa, 32, 64);
+  sx += __shfl_xor(sx, 32, 64);
+  sa *= 1.f / N;
+  sx *= 1.f / N;
+  const float nmr = -mean * rstd;  // (xh in its fma form below: see ln_treverse_t)
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int f0 = 32 * t + 8 * gq + 4 * h;
+      const float4 gv = *reinterpret_cast<const float4*>(gh + 32 * t + 8 * gq);
+      const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int q = 4 * gq + e;
+        const bool in = f0 + e < N;
+        const float xh = fmaf(lrelu(z[t][q]), rstd, nmr);
+        const float ad = zd[t][q];
+        zd[t][q] = in ? gg[e] * rstd * (ad - sa - xh * sx) : 0.f;
+      }
+    }
+}
+
+// Reverse of that block over primal and tangent (the closed form of misc.hip layernorm_tbwd_kernel, per row
+// in registers), in two steps so that only three H-vectors are worked on at a time.  With z the Dense
+// outputs, z' the Dense tangent, U / Ud the adjoints of the block's primal / tangent outputs u / u',
+// p = gamma Ud, gu = gamma U, a' = m z', q = mean(xh a'), t' = a' - mean(a') - xh q and
+// J(w) = rstd (w - mean(w) - xh mean(xh w)) the LayerNorm Jacobian (symmetric):
+//   adjoint of a' = J(p)
+//   adjoint of a  = J(gu + w) - rstd^2 xh mean(p t'),  w = -rstd (q p + mean(p xh) a')
+// (w and the last term: u' depends on the primal through xh and rstd).  LReLU has no second derivative off
+// the kink, so both adjoints pass through it as m.  Rows past M carry Ud = U = 0 and z' = 0: all zero.
+constexpr int LNGP_ACC = 6;  // column-sum accumulators of mlp_lngp_critic (VEC floats each, per wave)
+// acc[feature] += the colsum() value this lane owns (lanes l and l ^ 1 hold the same one: the even lane adds)
+__device__ __forceinline__ void col_add(float* acc, int t, float v, int lane, int h) {
+  if ((lane & 1) == 0) acc[32 * t + featq(colsum_q(lane), h)] += v;
+}
+struct LnT {
+  float mw, mwx, r2;  // mean(w), mean(w xh), rstd^2 mean(p t')
+};
+// Tangent step.  In: z, zd = z', Ud.  Out: zd <- the adjoint of z'; pg += column sums of the gamma gradient's
+// tangent part Ud rstd t' (= Ud u' / gamma, division free); W3: pw += column sums of u' (the head's gradient,
+// layer 2).  FIN (no primal adjoint U, layer 2): z <- the adjoint of z.  Otherwise Ud <- w and the row
+// scalars are returned for ln_treverse_p.
+template <int N, bool FIN, bool W3>
+__device__ __forceinline__ LnT ln_treverse_t(f32x16* z, f32x16* zd, f32x16* Ud, const float* gam, float mean,
+                                             float rstd, int h, int lane, float* pg, float* pw) {
+  constexpr int NT = (N + 31) / 32;
+  const float* gh = gam + 4 * h;
+  float sa = 0.f, sq = 0.f, sp = 0.f, spx = 0.f, spa = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int f0 = 32 * t + 8 * gq + 4 * h;
+      const float4 gv = *reinterpret_cast<const float4*>(gh + 32 * t + 8 * gq);
+      const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int q = 4 * gq + e;
+        const bool in = f0 + e < N;
+        const float zv = z[t][q];
+        const float xh = in ? (lrelu(zv) - mean) * rstd : 0.f;
+        const float ad = in ? (zv >= 0.f ? 1.f : LRELU_ALPHA_F) * zd[t][q] : 0.f;
+        const float p = in ? gg[e] * Ud[t][q] : 0.f;
+        zd[t][q] = ad;
+        sa += ad;
+        sq = fmaf(xh, ad, sq);
+        sp += p;
+        spx = fmaf(p, xh, spx);
+        spa = fmaf(p, ad, spa);
+      }
+    }
+  sa += __shfl_xor(sa, 32, 64);
+  sq += __shfl_xor(sq, 32, 64);
+  sp += __shfl_xor(sp, 32, 64);
+  spx += __shfl_xor(spx, 32, 64);
+  spa += __shfl_xor(spa, 32, 64);
+  // The second pass must not reuse the first one's per-element values: xh and p kept in registers are two
+  // more live H-vectors, and the kernel spills.  So a' went back into zd above, gamma is read again, and xh
+  // is formed as one fma (another expression than the first pass's: not merged with it; 1 ulp apart).
+  gh = reread(gh);
+  const float nmr = -mean * rstd;
+  constexpr float iN = 1.f / N;
+  sa *= iN; sq *= iN; sp *= iN; spx *= iN; spa *= iN;
+  LnT r;
+  r.mw = -rstd * (sq * sp + spx * sa);
+  r.mwx = -2.f * rstd * sq * spx;
+  r.r2 = rstd * rstd * (spa - sa * sp - sq * spx);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    f32x16 px, ud;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int f0 = 32 * t + 8 * gq + 4 * h;
+      const float4 gv = *reinterpret_cast<const float4*>(gh + 32 * t + 8 * gq);
+      const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int q = 4 * gq + e;
+        const bool in = f0 + e < N;
+        const float zv = z[t][q];
+        const float m = zv >= 0.f ? 1.f : LRELU_ALPHA_F;
+        const float xh = in ? fmaf(lrelu(zv), rstd, nmr) : 0.f;
+        const float ad = zd[t][q];
+        const float udv = in ? Ud[t][q] : 0.f;
+        const float p = gg[e] * udv;
+        const float tt = in ? rstd * (ad - sa - xh * sq) : 0.f;  // rstd t' = u' / gamma
+        const float wv = -rstd * (sq * p + spx * ad);
+        px[q] = udv * tt;
+        if constexpr (W3) ud[q] = gg[e] * tt;
+        zd[t][q] = in ? m * rstd * (p - sp - xh * spx) : 0.f;
+        if constexpr (FIN) z[t][q] = in ? m * (rstd * (wv - r.mw - xh * r.mwx) - r.r2 * xh) : 0.f;
+        else Ud[t][q] = wv;
+      }
+    }
+    col_add(pg, t, colsum(px, lane), lane, h);
+    if constexpr (W3) col_add(pw, t, colsum(ud, lane), lane, h);
+  }
+  return r;
+}
+// Primal step.  In: z, U, w (from ln_treverse_t) and its row scalars.  Out: z <- the adjoint of z;
+// pg += column sums of the gamma gradient's primal part U xh.
+template <int N>
+__device__ __forceinline__ void ln_treverse_p(f32x16* z, const f32x16* U, const f32x16* w, const LnT& r,
+                                              const float* gam, float mean, float rstd, int h, int lane, float* pg) {
+  constexpr int NT = (N + 31) / 32;
+  const float* gh = gam + 4 * h;
+  float sg = 0.f, sgx = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int f0 = 32 * t + 8 * gq + 4 * h;
+      const float4 gv = *reinterpret_cast<const float4*>(gh + 32 * t + 8 * gq);
+      const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int q = 4 * gq + e;
+        const bool in = f0 + e < N;
+        const float xh = in ? (lrelu(z[t][q]) - mean) * rstd : 0.f;
+        const float gu = in ? gg[e] * U[t][q] : 0.f;
+        sg += gu;
+        sgx = fmaf(gu, xh, sgx);
+      }
+    }
+  sg += __shfl_xor(sg, 32, 64);
+  sgx += __shfl_xor(sgx, 32, 64);
+  gh = reread(gh);  // (as in ln_treverse_t)
+  const float nmr = -mean * rstd;
+  const float mx = sg * (1.f / N) + r.mw, mxx = sgx * (1.f / N) + r.mwx;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    f32x16 px;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int f0 = 32 * t + 8 * gq + 4 * h;
+      const float4 gv = *reinterpret_cast<const float4*>(gh + 32 * t + 8 * gq);
+      const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int q = 4 * gq + e;
+        const bool in = f0 + e < N;
+        const float zv = z[t][q];
+        const float m = zv >= 0.f ? 1.f : LRELU_ALPHA_F;
+        const float xh = in ? fmaf(lrelu(zv), rstd, nmr) : 0.f;
+        const float uv = in ? U[t][q] : 0.f;
+        const float xb = fmaf(gg[e], uv, w[t][q]);
+        px[q] = uv * xh;
+        z[t][q] = in ? m * (rstd * (xb - mx - xh * mxx) - r.r2 * xh) : 0.f;
+      }
+    }
+    col_add(pg, t, colsum(px, lane), lane, h);
+  }
+}
+
+// The penalty's parameter gradient: d/dtheta sum_r s'_r, s'_r the tangent of the critic at x_hat_r along
+// v_r = c_b g_r (v held fixed; mlp_wgp_coef's c_b carries 2 lambda / B and the norm factor).
+//   tangent forward: z1' = v W1, u1' = LN1'(m1 z1'), z2' = u1' W2, u2' = LN2'(m2 z2'), s' = u2' . w3
+//   reverse from (adjoint of u2' = w3, adjoint of u2 = 0): ln_treverse_t at LN2, dgrad W2 of both adjoint
+//   streams, ln_treverse_t and ln_treverse_p at LN1 (now with a primal adjoint too).  No input gradient.
+// Writes the streaming weight-gradient operands (T): u1, u1d = u1' (X of gW2), dz2, dzt2 (dY of gW2),
+// dz1, dzt1 (dY of gW1; X = x_hat and g):
+//   gW2 = u1^T dz2 + u1d^T dzt2,  gW1 = x_hat^T dz1 + g^T dzt1
+// with dzt1 = c_b * (adjoint of z1'), so its X operand is g itself and v never goes to HBM.  The host passes
+// each pair as the two row blocks of one (2 M, .) buffer: one streaming product of 2 M rows per weight.  The
+// bias gradients gb1 = sum dz1, gb2 = sum dz2 are column sums here (of the primal rows only, in fp32 before
+// the operands are rounded), not the products' bias column, which would add the tangent rows.
+// lnslab rows (one per wave): dgamma1 | dbeta1 | dgamma2 | gw3 = sum u2' | gb1 | gb2 (dbeta2 = 0: u2 has no
+// adjoint; b3 gets nothing).
+// Register budget: at most four H-vectors are live (256 of the wave's 512 registers; the VALU reaches only
+// the 256 architectural ones), and the element-wise steps work on three.  So z1 and z1' are re-formed from
+// x_hat and g for the LN1 reverse (as mlp_wgan_critic recomputes y1), dz2 is read back from the operand just
+// stored for its dgrad instead of waiting in registers through LN1's tangent step (same lane, same
+// addresses, program order; the bf16 product rounds it to bf16 either way), and the six column-sum
+// accumulators live in LDS (6 VEC floats per wave, each feature owned by one lane) instead of 24 registers.
+template <typename T, int F, int H>
+__global__ void __launch_bounds__(MLP_THREADS) mlp_lngp_critic_kernel(
+    const T* __restrict__ x, const T* __restrict__ g, const float* __restrict__ cvec, MlpClip c, T* __restrict__ u1o,
+    T* __restrict__ u1do, T* __restrict__ dz2o, T* __restrict__ dzt2o, T* __restrict__ dz1o, T* __restrict__ dzt1o,
+    float* __restrict__ lnslab, int64_t M, int Tn) {
+  using Fr = typename MP<T>::frag;
+  constexpr int NTH = (H + 31) / 32, NTF = (F + 31) / 32;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  Fr* f1 = reinterpret_cast<Fr*>(lds);
+  Fr* f2 = f1 + fwd_entries<T, F, H>() * 64;
+  Fr* d2 = f2 + fwd_entries<T, H, H>() * 64;
+  float* vec = reinterpret_cast<float*>(d2 + dgrad_entries<T, H, H>() * 64);
+  build_fwd<T, F, H>(f1, c.W1);
+  build_fwd<T, H, H>(f2, c.W2);
+  build_dgrad<T, H, H>(d2, c.W2);
+  load_vec(vec + 0 * VEC, c.b1, H); load_vec(vec + 1 * VEC, c.g1, H); load_vec(vec + 2 * VEC, c.be1, H);
+  load_vec(vec + 3 * VEC, c.b2, H); load_vec(vec + 4 * VEC, c.g2, H); load_vec(vec + 5 * VEC, c.be2, H);
+  load_vec(vec + 6 * VEC, c.w3, H);
+  __syncthreads();
+  const float* gam1 = vec + 1 * VEC;
+  const float* gam2 = vec + 4 * VEC;
+  // this wave's column sums dgamma1 | dbeta1 | dgamma2 | gw3 | gb1 | gb2 (see col_add; written and read by
+  // this wave only)
+  float* accb = vec + CLIP_VECS * VEC + (threadIdx.x >> 6) * LNGP_ACC * VEC;
+  for (int i = threadIdx.x & 63; i < LNGP_ACC * VEC; i += 64) accb[i] = 0.f;
+  MLP_LOOP {
+    float* acc = const_cast<float*>(reread(accb));
+    float *pg1 = acc, *pb1 = acc + VEC, *pg2 = acc + 2 * VEC, *pw3 = acc + 3 * VEC;
+    float *pz1 = acc + 4 * VEC, *pz2 = acc + 5 * VEC;
+    const int64_t row = tile * 32 + (lane & 31);
+    const bool ok = row < M;
+    const float cb = ok ? cvec[row / Tn] : 0.f;
+    f32x16 xr[NTF], p0[NTH], p1[NTH], p2[NTH], p3[NTH];
+    float mean1, rstd1, mean2, rstd2;
+    // ---- layer 1, primal and tangent: p0 = z1, p1 = u1, p2 = z1' -> u1'
+    load_rows<T, F>(xr, x, row, M, h);
+    dense<T, F, H>(xr, p0, f1, lane);
+    bias_act<H>(p0, reread(vec + 0 * VEC), ACT_LINEAR, h);
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) p1[t] = p0[t];
+    lrelu_ln<H>(p1, reread(vec + 1 * VEC), reread(vec + 2 * VEC), h, mean1, rstd1);
+    store_rows<T, H>(u1o, row, M, p1, h);
+    load_rows<T, F>(xr, g, row, M, h);
+#pragma unroll
+    for (int t = 0; t < NTF; ++t) xr[t] *= cb;  // v
+    dense<T, F, H>(xr, p2, f1, lane);
+    ln_tangent<H>(p0, p2, reread(gam1), mean1, rstd1, h);
+    store_rows<T, H>(u1do, row, M, p2, h);
+    // ---- layer 2: p0 = z2, p3 = z2'
+    dense<T, H, H>(p1, p0, f2, lane);
+    bias_act<H>(p0, reread(vec + 3 * VEC), ACT_LINEAR, h);
+    dense<T, H, H>(p2, p3, f2, lane);
+    lrelu_stats<H>(p0, h, mean2, rstd2);
+    // ---- LN2 / LReLU reverse over primal and tangent: p0 <- dz2, p3 <- dzt2
+    head_rows<H>(p1, reread(vec + 6 * VEC), 1.f, ok, h);  // adjoint of u2' = w3 (0 on the rows past M)
+    ln_treverse_t<H, true, true>(p0, p3, p1, reread(gam2), mean2, rstd2, h, lane, pg2, pw3);
+    store_rows<T, H>(dz2o, row, M, p0, h);
+    store_rows<T, H>(dzt2o, row, M, p3, h);
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) col_add(pz2, t, colsum(p0[t], lane), lane, h);
+    // ---- LN1 / LReLU reverse, tangent step first: p2 = adjoint of u1', z1 and z1' again (p1, p3); then
+    // p3 <- adjoint of z1', p2 <- w
+    dense<T, H, H>(p3, p2, d2, lane);
+    load_rows<T, F>(xr, x, row, M, h);
+    dense<T, F, H>(xr, p1, f1, lane);
+    bias_act<H>(p1, reread(vec + 0 * VEC), ACT_LINEAR, h);
+    load_rows<T, F>(xr, g, row, M, h);
+#pragma unroll
+    for (int t = 0; t < NTF; ++t) xr[t] *= cb;
+    dense<T, F, H>(xr, p3, f1, lane);
+    const LnT lt = ln_treverse_t<H, false, false>(p1, p3, p2, reread(gam1), mean1, rstd1, h, lane, pg1, nullptr);
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) p3[t] *= cb;
+    store_rows<T, H>(dzt1o, row, M, p3, h);
+    // ---- primal step: p3 = adjoint of u1 = dz2 W2^T (dz2 back from its operand; the opaque row offset keeps
+    // the stored registers from being forwarded to the load, i.e. held); p1 <- dz1
+    {
+      int zz = 0;
+      asm volatile("" : "+v"(zz));
+      load_rows<T, H>(p0, dz2o, row + zz, M + zz, h);
+    }
+    dense<T, H, H>(p0, p3, d2, lane);
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) col_add(pb1, t, colsum(p3[t], lane), lane, h);
+    ln_treverse_p<H>(p1, p3, p2, lt, reread(gam1), mean1, rstd1, h, lane, pg1);
+    store_rows<T, H>(dz1o, row, M, p1, h);
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) col_add(pz1, t, colsum(p1[t], lane), lane, h);
+  }
+  // per-wave partials: lanes with bit 0 clear own feature featq(colsum_q(lane), h) of every tile
+  float* out = lnslab + ((int64_t)blockIdx.x * MLP_WAVES + (threadIdx.x >> 6)) * LNGP_ACC * H;
+  if ((lane & 1) == 0) {
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) {
+      const int f = 32 * t + featq(colsum_q(lane), h);
+      if (f < H) {
+#pragma unroll
+        for (int k = 0; k < LNGP_ACC; ++k) out[k * H + f] = accb[k * VEC + f];
+      }
+    }
+  }
+}
+
+// ===================================================================================================
 // fixed-order reductions
 // ===================================================================================================
 __global__ void __launch_bounds__(256) mlp_finish_kernel(const float* __restrict__ slab, int P,
@@ -2343,6 +2759,44 @@ void launch_mlp_wgan_critic_dx(int dt, const void* x, const MlpClip& cr, void* d
   });
   (void)H;
 }
+
+// ---- the LReLU + LayerNorm critic's gradient penalty (both dtypes; fp32 on the exact products: the split
+// planes of the three 100-wide images alone are 196 KB) ----
+void launch_mlp_lngp_norm(int dt, const void* x, const MlpClip& cr, void* xc, void* g, float* gsq, int64_t M, int F,
+                          int H, hipStream_t s) {
+  if (M <= 0) return;
+  MLP_DISPATCH(dt, F, {
+    auto k = mlp_lngp_norm_kernel<T, FF, 100>;
+    constexpr size_t lds = lds_wgan_critic_dx<T, FF, 100>();
+    set_lds(k, lds);
+    hipLaunchKernelGGL(k, dim3(mlp_grid(k, lds, M)), dim3(MLP_THREADS), lds, s, (const T*)x, cr, (T*)xc, (T*)g, gsq, M);
+  });
+  (void)H;
+}
+
+void launch_mlp_lngp_critic(int dt, const void* x, const void* g, const float* c, const MlpClip& cr, void* u1,
+                            void* u1d, void* dz2, void* dzt2, void* dz1, void* dzt1, float* lnslab, float* gg1,
+                            float* gbe1, float* gg2, float* gw3, float* gb1, float* gb2, int64_t M, int Tn, int F, int H,
+                            hipStream_t s) {
+  if (M <= 0) return;
+  MLP_DISPATCH(dt, F, {
+    auto k = mlp_lngp_critic_kernel<T, FF, 100>;
+    // the clip critic's plan plus the per-wave column-sum accumulators
+    constexpr size_t lds = lds_wgan_critic<T, FF, 100>() + (size_t)MLP_WAVES * LNGP_ACC * VEC * 4;
+    static_assert(lds <= 160 * 1024, "penalty critic images and accumulators exceed LDS");
+    set_lds(k, lds);
+    hipLaunchKernelGGL(k, dim3(slab_grid(k, lds, M)), dim3(MLP_THREADS), lds, s, (const T*)x, (const T*)g, c, cr, (T*)u1,
+                       (T*)u1d, (T*)dz2, (T*)dzt2, (T*)dz1, (T*)dzt1, lnslab, M, Tn);
+  });
+  // fixed-order sums of the per-wave rows [dgamma1 | dbeta1 | dgamma2 | gw3 | gb1 | gb2] into the gradients
+  const int P = mlp_slab_rows(M), L = 100;
+  hipLaunchKernelGGL(mlp_slab_sum_kernel, dim3((4 * L + 63) / 64), dim3(1024), 0, s, lnslab, P, (int64_t)LNGP_ACC * L, 0,
+                     L, 4, gg1, gbe1, gg2, gw3);
+  hipLaunchKernelGGL(mlp_slab_sum_kernel, dim3((2 * L + 63) / 64), dim3(1024), 0, s, lnslab, P, (int64_t)LNGP_ACC * L,
+                     4 * L, L, 2, gb1, gb2, (float*)nullptr, (float*)nullptr);
+  (void)H;
+}
+int mlp_lngp_slab_cols(int H) { return LNGP_ACC * H; }
 
 void launch_mlp_finish(const float* slab, int P, const float* e, int64_t n_e, int mode, float invB, const float* b3,
                        float lam, float* out, hipStream_t s) {

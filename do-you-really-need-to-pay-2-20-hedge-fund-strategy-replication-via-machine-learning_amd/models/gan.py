@@ -12,6 +12,7 @@ are kept as aliases (the GP file/class names are swapped upstream).
 | (lstm, gan)       | GAN/MTSS_GAN.py:127-157, class MTTS_GAN     | LSTM G                  | LSTM(100)->LSTM(100)->Dense(1,sigmoid)    |
 | (lstm, wgan)      | GAN/MTSS_WGAN.py:129-163, class MTTS_WGAN   | LSTM G                  | LSTM(lin)->LReLU->LN->LSTM(lin)->LReLU->LN->Dense(1) |
 | (lstm, wgan_gp)   | GAN/MTSS_WGAN_GP.py:221-252, class WGAN_GP  | LSTM G                  | LSTM(100)->LSTM(100)->Flatten->Dense(1)   |
+| (mlp_ln, wgan_gp) | framework variant (not in the reference)    | MLP G                   | the (mlp, wgan) LReLU + LN critic, GP     |
 | (conv, wgan_gp)   | north-star K14 (not in the reference)       | LSTM G                  | Conv1D x2 -> Flatten -> Dense(1)          |
 
 MLP G = Dense(100,sigmoid)->LReLU->LN->Dense(100,sigmoid)->LReLU->LN->Dense(F).
@@ -107,6 +108,11 @@ ZOO = {
     # framework variant: exercises the LayerNorm tangent kernels in the reverse-over-tangent critic step)
     ("lstm_ln", "wgan_gp"): ZooEntry(lstm_generator, lstm_critic_clip, "wgan_gp", "rmsprop", 5e-5, 5, gp_weight=10.0,
                                      save_prefix="MTSS_LN_GAN_GP", legacy_class="MTSS_LN_WGAN_GP"),
+    # the MLP WGAN's LReLU + LayerNorm critic trained with the gradient penalty instead of clipping (a
+    # framework variant: the MLP family's only GP model whose critic is not affine, so the penalty is a
+    # genuine per-row second-order pass -- fused in csrc/mlp.hip: mlp_lngp_norm / mlp_lngp_critic)
+    ("mlp_ln", "wgan_gp"): ZooEntry(mlp_generator, mlp_critic_clip, "wgan_gp", "rmsprop", 5e-5, 5, gp_weight=10.0,
+                                    save_prefix="LN_GAN_GP", legacy_class="MLP_LN_WGAN_GP"),
 }
 
 LEGACY = {e.legacy_class: k for k, e in ZOO.items()}
@@ -114,6 +120,7 @@ ALIASES = {
     "gan": ("mlp", "gan"), "wgan": ("mlp", "wgan"), "wgan_gp": ("mlp", "wgan_gp"),
     "mtss_gan": ("lstm", "gan"), "mtss_wgan": ("lstm", "wgan"), "mtss_wgan_gp": ("lstm", "wgan_gp"),
     "conv_wgan_gp": ("conv", "wgan_gp"), "mtss_ln_wgan_gp": ("lstm_ln", "wgan_gp"),
+    "ln_wgan_gp": ("mlp_ln", "wgan_gp"),
 }
 
 

@@ -87,7 +87,7 @@ class GANTrainer:
         self.gp_weight = cfg.gp_weight if cfg.gp_weight is not None else e.gp_weight
         T, F = cfg.window, cfg.features
         gkw = dict(seed=cfg.seed, dtype=param_dtype)
-        if cfg.arch != "mlp":
+        if not cfg.arch.startswith("mlp"):  # (mlp, mlp_ln: the MLP generator has no such variant)
             self.generator = e.generator(T, F, cfg.hidden, lrelu_after_first=cfg.lrelu_after_first, **gkw)
         else:
             self.generator = e.generator(T, F, cfg.hidden, **gkw)

@@ -1,9 +1,9 @@
-"""Fused MLP-GAN training steps (BASELINE configs 3 / 4 and the clipped MLP WGAN) on the kernels of
-``csrc/mlp.hip``.
+"""Fused MLP-GAN training steps (BASELINE configs 3 / 4, the clipped MLP WGAN and its LayerNorm critic
+under the gradient penalty) on the kernels of ``csrc/mlp.hip``.
 
 The layer-by-layer engine (``Sequential.efwd / ebwd / etfwd / etbwd``) runs one kernel per layer and
 pass and round-trips every (B*T, 100) activation and adjoint through HBM: 607 GB per bf16 MLP WGAN-GP
-iteration (``profiles/r06_mlp/baseline``).  For the three MLP models of the zoo this module replaces it
+iteration (``profiles/r06_mlp/baseline``).  For the four MLP models of the zoo this module replaces it
 with one kernel per pass that carries a 32-row tile through every layer in registers:
 
 * ``mlp_gen_fwd``     G(z) (GAN/WGAN_GP.py:221-236, GAN/GAN.py:127-142);
@@ -25,6 +25,12 @@ with one kernel per pass that carries a 32-row tile through every layer in regis
   the weight-gradient operands (u1, dz2, dz1) go to ``linear_wgrad_``, the LayerNorm and head gradients
   come from per-wave column-sum slabs; ``mlp_wgan_critic_dx`` is the generator step's dfake through that
   critic (then ``mlp_gen_bwd`` / ``mlp_gen_bwd_w`` as for the other two models);
+* ``mlp_lngp_norm`` + ``mlp_lngp_critic``  the gradient penalty of that LReLU + LayerNorm critic (zoo
+  ``("mlp_ln", "wgan_gp")``): g = dD/dx_hat per row with its squared norm, then (after ``mlp_wgp_coef``) the
+  reverse over the tangent along v = c_b g through both LayerNorms, as two row-stacked (primal; tangent)
+  weight-gradient operand pairs for ``linear_wgrad_`` and per-wave slabs for the LayerNorm, head and bias
+  gradients; the W terms of that update
+  are two ``mlp_wgan_critic`` launches (label -1 on real, +1 on fake);
 
 followed by the streaming weight-gradient kernels (``linear_wgrad_``) and the fused optimizer.  The
 random draws are the engine path's, in its order (real, noise, alpha per critic update), so both paths
@@ -116,11 +122,12 @@ def _clip_critic_lists(C, grad=False):
     return out + _views(C, L[6], ["kernel", "bias"], grad)
 
 
-_HEAD = {"wgan_gp": 0, "gan": 1, "wgan": 2}  # 2: the clip critic (per-row LReLU + LN, W loss)
+# 2: the clip critic (per-row LReLU + LN, W loss); 3: that critic under the gradient penalty
+_HEAD = {("mlp", "wgan_gp"): 0, ("mlp", "gan"): 1, ("mlp", "wgan"): 2, ("mlp_ln", "wgan_gp"): 3}
 
 
 def _critic_of(C, head: int, grad=False):
-    return _clip_critic_lists(C, grad) if head == 2 else _critic_lists(C, head, grad)
+    return _clip_critic_lists(C, grad) if head in (2, 3) else _critic_lists(C, head, grad)
 
 
 class FusedMLP:
@@ -128,7 +135,7 @@ class FusedMLP:
 
     def __init__(self, tr):
         self.tr = tr
-        self.head = _HEAD[tr.cfg.loss]
+        self.head = _HEAD[(tr.cfg.arch, tr.cfg.loss)]
         self.gw, self.gg = _gen_lists(tr.generator), _gen_lists(tr.generator, grad=True)
         self.cw, self.cg = _critic_of(tr.critic, self.head), _critic_of(tr.critic, self.head, grad=True)
         self._ones = {}
@@ -155,7 +162,7 @@ class FusedMLP:
     def decline_reason(tr) -> str | None:
         """Why this trainer does not get the fused path (None: it does)."""
         cfg = tr.cfg
-        if cfg.arch != "mlp" or cfg.loss not in _HEAD:
+        if (cfg.arch, cfg.loss) not in _HEAD:
             return "not an MLP model of the zoo"
         if tr.device.type != "cuda":
             return "device is not a GPU"
@@ -167,7 +174,7 @@ class FusedMLP:
             return "native library not in use"
         if not bool(_ops().mlp_supported(int(cfg.features), int(cfg.hidden))):
             return f"width (F, H) = ({int(cfg.features)}, {int(cfg.hidden)}) not instantiated"
-        if _gen_lists(tr.generator) is None or _critic_of(tr.critic, _HEAD[cfg.loss]) is None:
+        if _gen_lists(tr.generator) is None or _critic_of(tr.critic, _HEAD[(cfg.arch, cfg.loss)]) is None:
             return "structure mismatch (generator or critic is not the zoo's layer sequence)"
         return None
 
@@ -177,7 +184,7 @@ class FusedMLP:
         if why is None:
             return True
         # one line per trainer, for an MLP model on a GPU only (elsewhere the engine is the expected path)
-        if tr.cfg.arch == "mlp" and tr.device.type == "cuda" and not getattr(tr, "_fused_decline_logged", False):
+        if tr.cfg.arch.startswith("mlp") and tr.device.type == "cuda" and not getattr(tr, "_fused_decline_logged", False):
             tr._fused_decline_logged = True
             log.warning("fused MLP path declined for (%s, %s): %s; running the layer-by-layer engine",
                         tr.cfg.arch, tr.cfg.loss, why)
@@ -200,7 +207,7 @@ class FusedMLP:
             else:
                 dfake, slab = ops.mlp_critic_dx(fake, self.cw, 0, -1.0)
             loss = ops.mlp_finish(slab, None, 1, 1.0 / B, self.cw[5], 0.0)
-        elif self.head == 2:
+        elif self.head in (2, 3):
             dfake, slab = ops.mlp_wgan_critic_dx(fake, self.cw)  # slab: sum of -s over the rows
             loss = ops.mlp_finish(slab, None, 2, 1.0 / noise[..., 0].numel(), None, 0.0)
         else:
@@ -279,6 +286,45 @@ class FusedMLP:
         tr._g_acc = self._generator_grads(noise, fake).to(tr._acc)
         tr._apply(tr.generator)
 
+    # ---- the LReLU + LayerNorm critic with the gradient penalty ((mlp_ln, wgan_gp)) --------------------
+    def _lngp_critic_grads(self, real, fake, alpha):
+        """Accumulate the critic gradient of W(real, -1) + W(fake, +1) + lambda GP(x_hat); returns the loss
+        pack [total, W real, W fake, GP] (the W terms: means over the B*T rows, as the engine's)."""
+        tr, ops = self.tr, _ops()
+        B, lam = real.shape[0], float(tr.gp_weight)
+        wr = self._wgan_critic_grads(real, -1.0)
+        wf = self._wgan_critic_grads(fake, 1.0)
+        xh = Fn.interpolate(real, fake, alpha)
+        xg, gsq = ops.mlp_lngp_norm(xh, self.cw)  # xg = [x_hat; g]
+        c, e = ops.mlp_wgp_coef(gsq, lam)
+        # row-stacked primal / tangent operand pairs: one streaming product of 2 B T rows per weight; the bias
+        # gradients (primal rows only: z' = u' W has no bias) come from the kernel's column sums
+        U, DZ2, DZ1 = ops.mlp_lngp_critic(xg, c, self.cw, self.cg)
+        Fn.linear_wgrad_(xg, DZ1, self.cg[0], None)
+        Fn.linear_wgrad_(U, DZ2, self.cg[4], None)
+        pen = ops.mlp_finish(self._zero_slab(), e, 0, 1.0 / B, None, lam)[3]  # mean_b (|g_b| - 1)^2, fixed order
+        return torch.stack([wr + wf + lam * pen, wr, wf, pen])
+
+    def _zero_slab(self):
+        t = self._ones.get("zero_slab")
+        if t is None:
+            t = self._ones["zero_slab"] = torch.zeros((1, 2), dtype=torch.float32, device=self.tr.device)
+        return t
+
+    def _step_lngp(self):
+        tr, ops = self.tr, _ops()
+        B = tr.cfg.batch_size
+        for _ in range(tr.n_critic):
+            real, noise = tr._batch(B)
+            fake = ops.mlp_gen_fwd(noise, self.gw)
+            alpha = tr.rng.uniform((B,))
+            tr._d_acc = self._lngp_critic_grads(real, fake, alpha).to(tr._acc)
+            tr._apply(tr.critic)
+        # the generator step trains on the last critic update's noise with the same generator weights: its
+        # fake windows are that update's (as the clipped WGAN's step above)
+        tr._g_acc = self._generator_grads(noise, fake).to(tr._acc)
+        tr._apply(tr.generator)
+
     # ---- vanilla GAN (config 3) -------------------------------------------------------------------
     def _gan_d_grads(self, x, label: float):
         """Accumulate the discriminator gradient of BCE(D(x), label) (mean over the B*T rows); returns
@@ -319,5 +365,7 @@ class FusedMLP:
             self._step_wgan_gp()
         elif self.head == 2:
             self._step_wgan()
+        elif self.head == 3:
+            self._step_lngp()
         else:
             self._step_gan()

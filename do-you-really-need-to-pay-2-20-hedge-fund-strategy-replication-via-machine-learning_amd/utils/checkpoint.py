@@ -72,7 +72,7 @@ def build_generator_from_config(cfg: dict, device="cpu"):
 
     arch = cfg.get("arch", "lstm")
     T, F, H = cfg["window"], cfg["features"], cfg.get("hidden", 100)
-    if arch == "mlp":
+    if arch.startswith("mlp"):  # (mlp, mlp_ln: one MLP generator)
         return zoo.mlp_generator(T, F, H, device=device)
     return zoo.lstm_generator(T, F, H, lrelu_after_first=cfg.get("lrelu_after_first", False), device=device)
 
