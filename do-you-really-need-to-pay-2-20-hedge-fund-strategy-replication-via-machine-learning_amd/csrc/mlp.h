@@ -1,7 +1,7 @@
-// Fused MLP-GAN passes (csrc/mlp.hip): host launchers for BASELINE configs 3 / 4 (the vanilla GAN of
+// Fused MLP-GAN passes (csrc/mlp_*.hip): host launchers for BASELINE configs 3 / 4 (the vanilla GAN of
 // GAN/GAN.py and the MLP WGAN-GP of GAN/WGAN_GP.py), the clipped MLP WGAN of GAN/WGAN.py and its critic under
 // the gradient penalty.  Included
-// only by mlp.hip and bindings_mlp.cpp.
+// only by the MLP sources (mlp_dev.h, mlp_*.hip) and bindings_mlp.cpp.
 //
 // Every launcher takes the fp32 master weights (Keras layout: kernel (in, out), row-major) and
 // activations of dtype `dt` (DT_F32 / DT_BF16) as row-major (M, features) matrices, M = B * T rows.
@@ -43,12 +43,12 @@ void launch_mlp_wgp_norm(int dt, const MlpCritic& c, float* gsq, int64_t M, int 
 int mlp_wgp_coef_parts(int64_t B);
 void launch_mlp_wgp_coef(const float* gsq, int Tn, int64_t B, float lam, float* c, float* e, hipStream_t s);
 // the WGAN-GP critic step of the linear critic on one row tile: W terms on real / fake and the
-// reverse-over-tangent GP term, as combined wgrad operands (see mlp.hip)
+// reverse-over-tangent GP term, as combined wgrad operands (see mlp_affine.hip)
 void launch_mlp_wgp_critic(int dt, const void* real, const void* fake, const float* c, const MlpCritic& cr,
                            void* X2c, void* dY2, void* X1c, void* dY1, void* Y3c, float* slab, int64_t M, int Tn,
                            int F, int H, hipStream_t s);
-// critic input gradient for the generator step: dx = dL/dx with the Wasserstein (head 0, label -1)
-// or BCE (head 1, label `label`) loss; slab: loss partials
+// critic input gradient for the generator step: dx = dL/dx with the Wasserstein (head 0, label -1; `label`
+// unused) or BCE (head 1, label `label`) loss; slab: loss partials
 void launch_mlp_critic_dx(int dt, int head, const void* x, const MlpCritic& cr, float label, void* dx, float* slab,
                           int64_t M, int Tn, int F, int H, hipStream_t s);
 // discriminator update of the vanilla GAN (head 1, BCE with label `label`): wgrad operands
@@ -90,16 +90,15 @@ void launch_mlp_lngp_critic(int dt, const void* x, const void* g, const float* c
 void launch_mlp_finish(const float* slab, int P, const float* e, int64_t n_e, int mode, float invB, const float* b3,
                        float lam, float* out, hipStream_t s);
 // fixed-order column sums of a (P, L) slab added into out[L]; the 4-segment form adds segment k of
-// every (P, 4 L) slab row into o_k (nullptr: skipped)
+// every (P, 4 L) slab row into o_k (nullptr: skipped); _segs: nseg <= 4 segments of L columns from col0 of
+// rows of `stride` floats
+void launch_mlp_slab_sum_segs(const float* slab, int P, int64_t stride, int col0, int L, int nseg, float* o0, float* o1,
+                              float* o2, float* o3, hipStream_t s);
 void launch_mlp_slab_sum(const float* slab, int P, int L, float* out, hipStream_t s);
 void launch_mlp_slab_sum4(const float* slab, int P, int L, float* o0, float* o1, float* o2, float* o3, hipStream_t s);
 // out[j] += sum_p slab[p * stride + col0 + j], j < L (fixed order)
 void launch_mlp_slab_sum_cols(const float* slab, int P, int64_t stride, int col0, int L, float* out, hipStream_t s);
 
-// The GP critic update with its three weight gradients accumulated in the kernel (bf16 only; the LDS
-// plan must fit: T <= 34 at F = 32, T <= 18 at F = 36, mlp_wgpw_supported).  Launches mlp_wgpw_blocks(M) workgroups; gslab
-// (blocks x (H + F + T) H fp32) gets each workgroup's partial [gW2 | gW1 | gw3], slab (4 blocks x 2)
-// the per-wave W-loss partials of mlp_wgp_critic.  Every slab element is written.
 // The generator reverse with its parameter gradients accumulated in the kernel (bf16, F in {32, 36}):
 // mlp_gbw_blocks(M) workgroups; gslab rows (one per workgroup) = [W1 F x H][b1 H][W2 H x H][b2 H]
 // [W3 H x F][b3 F] partials, lnslab (4 rows per workgroup, 4 H) = the LayerNorm partials of
@@ -123,7 +122,7 @@ size_t mlp_wgpt_tsum_floats(int F, int Tn);
 void launch_mlp_wgp_critic_t(int dt, const void* real, const void* fake, const float* c, const MlpCritic& cr,
                              float* tslab, float* tsum, float* slab, int64_t Bn, int Tn, int F, float* gW1, float* gW2,
                              float* gw3, hipStream_t s);
-// The affine critic's update from batch sums (both dtypes; csrc/mlp.hip mlp_wgp_affine_kernel): per-t
+// The affine critic's update from batch sums (both dtypes; csrc/mlp_affine.hip mlp_wgp_affine_kernel): per-t
 // column sums of real and fake -> one-workgroup fp32 finish; gW1 / gW2 / gw3 accumulate, slab (1 x 2) =
 // the real / fake score sums, e (1) = B (1 - |g|)^2.  ws: mlp_affine_ws_floats floats of scratch.
 // critic_dx_affine: the generator step's dfake (-g_t / B broadcast over the batch) and its score slab.
@@ -136,9 +135,5 @@ void launch_mlp_critic_dx_affine(int dt, const void* fake, const MlpCritic& cr, 
 int mlp_gbw_blocks(int64_t M);
 void launch_mlp_gen_bwd_w(const void* noise, const void* dfake, const MlpGen& g, float* gslab, float* lnslab, int64_t M,
                           int F, hipStream_t s);
-bool mlp_wgpw_supported(int F, int Tn);
-int mlp_wgpw_blocks(int64_t M);
-void launch_mlp_wgp_critic_w(const void* real, const void* fake, const float* c, const MlpCritic& cr, float* gslab,
-                             float* slab, int64_t M, int Tn, int F, hipStream_t s);
 
 }  // namespace hfrep

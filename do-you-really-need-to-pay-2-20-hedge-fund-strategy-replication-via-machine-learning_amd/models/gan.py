@@ -110,7 +110,7 @@ ZOO = {
                                      save_prefix="MTSS_LN_GAN_GP", legacy_class="MTSS_LN_WGAN_GP"),
     # the MLP WGAN's LReLU + LayerNorm critic trained with the gradient penalty instead of clipping (a
     # framework variant: the MLP family's only GP model whose critic is not affine, so the penalty is a
-    # genuine per-row second-order pass -- fused in csrc/mlp.hip: mlp_lngp_norm / mlp_lngp_critic)
+    # genuine per-row second-order pass -- fused in csrc/mlp_clip.hip: mlp_lngp_norm / mlp_lngp_critic)
     ("mlp_ln", "wgan_gp"): ZooEntry(mlp_generator, mlp_critic_clip, "wgan_gp", "rmsprop", 5e-5, 5, gp_weight=10.0,
                                     save_prefix="LN_GAN_GP", legacy_class="MLP_LN_WGAN_GP"),
 }

@@ -1,5 +1,5 @@
 """Fused MLP-GAN training steps (BASELINE configs 3 / 4, the clipped MLP WGAN and its LayerNorm critic
-under the gradient penalty) on the kernels of ``csrc/mlp.hip``.
+under the gradient penalty) on the kernels of ``csrc/mlp_*.hip``.
 
 The layer-by-layer engine (``Sequential.efwd / ebwd / etfwd / etbwd``) runs one kernel per layer and
 pass and round-trips every (B*T, 100) activation and adjoint through HBM: 607 GB per bf16 MLP WGAN-GP
@@ -11,9 +11,8 @@ with one kernel per pass that carries a 32-row tile through every layer in regis
   sample and the adjoint coefficient c_b (GAN/WGAN_GP.py:201-216);
 * ``mlp_wgp_critic``  a whole WGAN-GP critic update of the linear critic (GAN/WGAN_GP.py:238-253):
   W terms on real / fake and the reverse-over-tangent of the penalty, as one combined weight-gradient
-  operand per weight (see the kernel's comment); in bf16 ``mlp_wgp_critic_w`` also accumulates the
-  three weight gradients in the kernel (128-row block tiles staged transposed in LDS), in fp32
-  ``mlp_wgp_critic_t`` (rows walked t-major, per-t column sums in registers);
+  operand per weight (see the kernel's comment); ``mlp_wgp_critic_t`` also takes the three weight
+  gradients in the kernel (rows walked t-major, per-t column sums in registers);
 * ``mlp_gan_critic``  a vanilla-GAN discriminator update (GAN/GAN.py:144-158, 187-189);
   ``mlp_gan_critic_g`` takes its gradients in the kernel as dz-weighted column sums (the linear hidden
   layers make every adjoint of a row rank-1);
@@ -69,21 +68,28 @@ def _views(model, layer, names, grad=False):
     return [get(layer, n) for n in names]
 
 
-def _gen_lists(G, grad=False):
-    """[W1, b1, gamma1, beta1, W2, b2, gamma2, beta2, W3, b3] of the MLP generator, or None if G is
-    not Dense(s) -> LReLU -> LN -> Dense(s) -> LReLU -> LN -> Dense."""
-    L = G.layers
+def _ln_stack_lists(M, hidden_act: int, last_ok, grad=False):
+    """[W1, b1, gamma1, beta1, W2, b2, gamma2, beta2, W3, b3] of Dense -> LReLU(0.2) -> LN(1e-3) -> Dense ->
+    LReLU(0.2) -> LN(1e-3) -> Dense (every Dense with bias, the first two with activation ``hidden_act``, the
+    last one linear and accepted by ``last_ok``), or None if M is not that."""
+    L = M.layers
     kinds = [Dense, LeakyReLU, LayerNormalization, Dense, LeakyReLU, LayerNormalization, Dense]
     if len(L) != 7 or not all(isinstance(l, k) for l, k in zip(L, kinds)):
         return None
-    if not (L[0].act_code == 1 and L[3].act_code == 1 and L[6].act_code == 0 and all(L[i].use_bias for i in (0, 3, 6))):
+    if not (L[0].act_code == hidden_act and L[3].act_code == hidden_act and L[6].act_code == 0
+            and all(L[i].use_bias for i in (0, 3, 6)) and last_ok(L[6])):
         return None
     if abs(L[1].alpha - 0.2) > 1e-6 or abs(L[4].alpha - 0.2) > 1e-6 or L[2].eps != 1e-3 or L[5].eps != 1e-3:
         return None
     out = []
     for d, ln in ((L[0], L[2]), (L[3], L[5])):
-        out += _views(G, d, ["kernel", "bias"], grad) + _views(G, ln, ["gamma", "beta"], grad)
-    return out + _views(G, L[6], ["kernel", "bias"], grad)
+        out += _views(M, d, ["kernel", "bias"], grad) + _views(M, ln, ["gamma", "beta"], grad)
+    return out + _views(M, L[6], ["kernel", "bias"], grad)
+
+
+def _gen_lists(G, grad=False):
+    """The MLP generator: sigmoid Dense layers in front of each LReLU -> LN, any output width."""
+    return _ln_stack_lists(G, 1, lambda last: True, grad)
 
 
 def _critic_lists(C, head: int, grad=False):
@@ -105,21 +111,8 @@ def _critic_lists(C, head: int, grad=False):
 
 
 def _clip_critic_lists(C, grad=False):
-    """[W1, b1, gamma1, beta1, W2, b2, gamma2, beta2, w3, b3] of the clipped WGAN's critic, or None if C
-    is not Dense(linear) -> LReLU(0.2) -> LN(1e-3) -> Dense(linear) -> LReLU(0.2) -> LN(1e-3) -> Dense(1)
-    (per row, no Flatten; every Dense with bias)."""
-    L = C.layers
-    kinds = [Dense, LeakyReLU, LayerNormalization, Dense, LeakyReLU, LayerNormalization, Dense]
-    if len(L) != 7 or not all(isinstance(l, k) for l, k in zip(L, kinds)):
-        return None
-    if not (all(L[i].act_code == 0 and L[i].use_bias for i in (0, 3, 6)) and L[6].units == 1):
-        return None
-    if abs(L[1].alpha - 0.2) > 1e-6 or abs(L[4].alpha - 0.2) > 1e-6 or L[2].eps != 1e-3 or L[5].eps != 1e-3:
-        return None
-    out = []
-    for d, ln in ((L[0], L[2]), (L[3], L[5])):
-        out += _views(C, d, ["kernel", "bias"], grad) + _views(C, ln, ["gamma", "beta"], grad)
-    return out + _views(C, L[6], ["kernel", "bias"], grad)
+    """The clipped WGAN's critic: linear Dense layers, per-row Dense(1) head (no Flatten)."""
+    return _ln_stack_lists(C, 0, lambda last: last.units == 1, grad)
 
 
 # 2: the clip critic (per-row LReLU + LN, W loss); 3: that critic under the gradient penalty
@@ -140,23 +133,19 @@ class FusedMLP:
         self.cw, self.cg = _critic_of(tr.critic, self.head), _critic_of(tr.critic, self.head, grad=True)
         self._ones = {}
         # GP critic update (both dtypes): rows walked t-major, the weight gradients as per-t column sums
-        # in registers (mlp_wgp_critic_t) -- no per-row operands in HBM.  HFREP_MLP_WGRAD_TSUM=0 takes
-        # the bf16 kernel that stages 128-row tiles transposed in LDS instead (mlp_wgp_critic_w, A/B:
-        # 4 % slower on config 4, profiles/r06_wgpw/tsum); HFREP_MLP_WGRAD_INKERNEL=0 keeps the operand
-        # path (mlp_wgp_critic + linear_wgrad_).  The generator reverse: mlp_gen_bwd_w (bf16).
+        # in registers (mlp_wgp_critic_t) -- no per-row operands in HBM.  HFREP_MLP_WGRAD_INKERNEL=0 keeps
+        # the operand path (mlp_wgp_critic + linear_wgrad_).  The generator reverse: mlp_gen_bwd_w (bf16).
         cfg = tr.cfg
         on = os.environ.get("HFREP_MLP_WGRAD_INKERNEL", "1") != "0"
         inkernel = tr.dtype == torch.bfloat16 and on
-        self.wgrad_inkernel = (inkernel and self.head == 0 and os.environ.get("HFREP_MLP_WGRAD_TSUM", "1") == "0"
-                               and bool(_ops().mlp_wgpw_supported(int(cfg.features), int(cfg.window))))
-        self.wgrad_tsum = self.head == 0 and on and not self.wgrad_inkernel
+        self.wgrad_tsum = self.head == 0 and on
         # affine critic: the update from per-t batch sums (mlp_wgp_affine / mlp_critic_dx_affine)
         self.affine = (self.head == 0 and os.environ.get("HFREP_MLP_AFFINE", "1") != "0"
                        and bool(_ops().mlp_affine_supported(int(cfg.features), int(cfg.window))))
         self.gen_wgrad_inkernel = inkernel
         # GAN discriminator: rank-1 adjoints per row -> gradients as dz-weighted column sums in the
         # kernel (mlp_gan_critic_g, both dtypes); HFREP_MLP_WGRAD_INKERNEL=0 keeps the operand path
-        self.gan_colsum = self.head == 1 and os.environ.get("HFREP_MLP_WGRAD_INKERNEL", "1") != "0"
+        self.gan_colsum = self.head == 1 and on
 
     @staticmethod
     def decline_reason(tr) -> str | None:
@@ -235,9 +224,8 @@ class FusedMLP:
         gsq = ops.mlp_wgp_norm(real, self.cw)
         c, e = ops.mlp_wgp_coef(gsq, float(tr.gp_weight))
         gW1, _gb1, gW2, _gb2, gw3, _gb3 = self.cg
-        if self.wgrad_inkernel or self.wgrad_tsum:
-            op = ops.mlp_wgp_critic_w if self.wgrad_inkernel else ops.mlp_wgp_critic_t
-            slab = op(real, fake, c, self.cw, gW1, gW2, gw3)
+        if self.wgrad_tsum:
+            slab = ops.mlp_wgp_critic_t(real, fake, c, self.cw, gW1, gW2, gw3)
             return ops.mlp_finish(slab, e, 0, 1.0 / B, self.cw[5], float(tr.gp_weight))
         X2c, dY2, X1c, dY1, Y3c, slab = ops.mlp_wgp_critic(real, fake, c, self.cw)
         # the W terms' bias gradients cancel (-1/B and +1/B per row pair) and the tangent has none

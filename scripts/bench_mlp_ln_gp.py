@@ -1,5 +1,5 @@
 """A/B timing of the training step of the MLP WGAN-GP with the LReLU + LayerNorm critic, zoo
-("mlp_ln", "wgan_gp"): fused kernels (csrc/mlp.hip mlp_lngp_norm / mlp_lngp_critic) vs the layer-by-layer engine.
+("mlp_ln", "wgan_gp"): fused kernels (csrc/mlp_clip.hip mlp_lngp_norm / mlp_lngp_critic) vs the layer-by-layer engine.
 
 bench.py has no entry for this model; this script times ``GANTrainer.train_step`` with device
 events after warm-up, for each dtype the fused path first and then the engine path

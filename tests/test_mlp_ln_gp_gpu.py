@@ -1,4 +1,4 @@
-"""Fused WGAN-GP step of the LReLU + LayerNorm MLP critic, zoo ``("mlp_ln", "wgan_gp")`` (csrc/mlp.hip
+"""Fused WGAN-GP step of the LReLU + LayerNorm MLP critic, zoo ``("mlp_ln", "wgan_gp")`` (csrc/mlp_*.hip
 mlp_lngp_norm / mlp_lngp_critic, train/mlp_fused.py head 3) vs the CPU fp64 explicit engine and the GPU engine
 path.
 

@@ -1,4 +1,4 @@
-"""Fused clipped-WGAN kernels (csrc/mlp.hip mlp_wgan_critic / mlp_wgan_critic_dx, train/mlp_fused.py)
+"""Fused clipped-WGAN kernels (csrc/mlp_clip.hip mlp_wgan_critic / mlp_wgan_critic_dx, train/mlp_fused.py)
 vs the CPU fp64 explicit engine and the GPU engine path.
 
 The clipped MLP WGAN of GAN/WGAN.py: per-row critic Dense -> LReLU -> LN -> Dense -> LReLU -> LN ->
