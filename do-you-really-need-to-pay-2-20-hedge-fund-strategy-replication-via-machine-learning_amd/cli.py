@@ -204,7 +204,7 @@ def cmd_eval(a) -> int:
     real = np.load(a.real, allow_pickle=False)
     fake = np.load(a.fake, allow_pickle=False)
     n = min(len(real), len(fake))
-    ev = _evaluator(real[:n], fake[:n], a.name)
+    ev = _evaluator(real[:n], fake[:n], a.name, device=a.device)
     if a.metrics:
         res = {m: float(np.asarray(getattr(ev, m)()).mean()) for m in a.metrics.split(",")}
     else:
@@ -217,11 +217,12 @@ def cmd_eval(a) -> int:
     return 0
 
 
-def _evaluator(real, fake, name="model"):
-    """GANEval with the reference constructor (real, fake, dataset, subplot_title, model_name)."""
+def _evaluator(real, fake, name="model", device=None):
+    """GANEval with the reference constructor (real, fake, dataset, subplot_title, model_name); ``device``
+    (e.g. ``'cuda'``) runs the large-N metrics on the GPU, None or ``'cpu'`` the reference formulas."""
     from .eval.gan_eval import GANEval
 
-    return GANEval(real, fake, real, [f"feature_{i}" for i in range(real.shape[-1])], [name])
+    return GANEval(real, fake, real, [f"feature_{i}" for i in range(real.shape[-1])], [name], device=device)
 
 
 def wasserstein_parity(real_train, real_holdout, fake, seed=0):
@@ -432,6 +433,8 @@ def main(argv=None) -> int:
     e.add_argument("--name", default="model")
     e.add_argument("--metrics", default=None, help="comma list (default: run_all)")
     e.add_argument("--out", default=None)
+    e.add_argument("--device", default=None,
+                   help="run the large-N metrics on this device, e.g. cuda (default: the host formulas)")
     c = sub.add_parser("clean", help="raw data -> cleaned_data CSVs")
     c.add_argument("--raw", required=True)
     c.add_argument("--out", required=True)

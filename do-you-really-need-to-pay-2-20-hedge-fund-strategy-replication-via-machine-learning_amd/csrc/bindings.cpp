@@ -995,6 +995,84 @@ Tensor wdist_sorted(Tensor x, Tensor ref_sorted) {
   return out;
 }
 
+// ------------------------------------------------------------------------------------ eval metrics
+// csrc/evalm.hip: float64 results of fp32 inputs, stream-ordered, no host synchronise, deterministic
+Tensor ks_stat(Tensor x, Tensor ref_sorted) {
+  CHECK_F32(x); CHECK_F32(ref_sorted);
+  TORCH_CHECK(x.dim() == 2, "ks_stat: x must be (n, F)");
+  const int64_t n = x.size(0), F = x.size(1);
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 24), "ks_stat: 1 <= n <= 2^24, got n = ", n);
+  TORCH_CHECK(F >= 1 && F <= 1024, "ks_stat: 1 <= F <= 1024, got F = ", F);
+  TORCH_CHECK(ref_sorted.device() == x.device() && ref_sorted.dim() == 2 && ref_sorted.size(0) == F &&
+                  ref_sorted.size(1) == n,
+              "ks_stat: ref_sorted must be (F, n) = (", F, ", ", n, ") fp32 on x's device");
+  GUARD(x);
+  const auto f64 = x.options().dtype(at::kDouble);
+  Tensor out = out_empty({F}, f64);
+  Tensor ws = out_empty({F, n}, x.options());  // sorted 32-bit keys; ws2: the merge passes' other buffer
+  Tensor ws2 = out_empty({n > 16384 ? F : 0, n}, x.options());
+  Tensor slab = out_empty({F, 2, (int64_t)hfrep::ks_blocks((int)n)}, f64);
+  hfrep::launch_ks_stat(x.data_ptr<float>(), ref_sorted.data_ptr<float>(), reinterpret_cast<uint32_t*>(ws.data_ptr()),
+                        reinterpret_cast<uint32_t*>(ws2.data_ptr()), slab.data_ptr<double>(), out.data_ptr<double>(), (int)n, (int)F, cur_stream(x));
+  return out;
+}
+
+Tensor acf_mean(Tensor x, int64_t nlags) {
+  CHECK_F32(x);
+  TORCH_CHECK(x.dim() == 3 && x.size(0) >= 1 && x.size(1) >= 1 && x.size(2) >= 1, "acf_mean: x must be (N, T, F)");
+  const int64_t N = x.size(0), T = x.size(1), F = x.size(2);
+  TORCH_CHECK(N <= INT32_MAX && nlags >= 0 && nlags <= 4096 && T <= 65536 && F <= 65536 &&
+                  hfrep::acf_supported((int)T, (int)F, (int)nlags),
+              "acf_mean: the (T, F) window and the (nlags + 1) F accumulators must fit 160 KB of LDS, got T = ", T,
+              ", F = ", F, ", nlags = ", nlags);
+  GUARD(x);
+  const auto f64 = x.options().dtype(at::kDouble);
+  Tensor out = out_empty({F, nlags + 1}, f64);
+  Tensor slab = out_empty({(int64_t)hfrep::acf_blocks((int)N), (nlags + 1) * F}, f64);
+  hfrep::launch_acf_mean(x.data_ptr<float>(), slab.data_ptr<double>(), out.data_ptr<double>(), (int)N, (int)T, (int)F,
+                         (int)nlags, cur_stream(x));
+  return out;
+}
+
+Tensor nb_divergences(Tensor real, Tensor fake, Tensor theta, Tensor var, Tensor log_prior) {
+  CHECK_F32(real); CHECK_F32(fake);
+  TORCH_CHECK(real.dim() == 3 && real.size(0) >= 1 && real.sizes() == fake.sizes() && fake.device() == real.device(),
+              "nb_divergences: real and fake must be (N, T, F) on one device");
+  const int64_t N = real.size(0), T = real.size(1), F = real.size(2);
+  TORCH_CHECK(N <= INT32_MAX && T <= 168 && F <= 64 && hfrep::nb_supported((int)T, (int)F),
+              "nb_divergences: F <= 64 and T <= 168, got T = ", T,
+              ", F = ", F);
+  for (const Tensor* t : {&theta, &var, &log_prior})
+    TORCH_CHECK(t->is_cuda() && t->device() == real.device() && t->scalar_type() == at::kDouble && t->is_contiguous(),
+                "nb_divergences: theta, var and log_prior must be contiguous float64 tensors on real's device");
+  TORCH_CHECK(theta.dim() == 2 && theta.size(0) == F && theta.size(1) == T && var.sizes() == theta.sizes() &&
+                  log_prior.dim() == 1 && log_prior.size(0) == F,
+              "nb_divergences: theta, var (F, T) and log_prior (F,)");
+  GUARD(real);
+  const auto f64 = real.options().dtype(at::kDouble);
+  Tensor out = out_empty({4}, f64);
+  Tensor slab = out_empty({(int64_t)hfrep::nb_slab_rows((int)N), 4}, f64);
+  hfrep::launch_nb_divergences(real.data_ptr<float>(), fake.data_ptr<float>(), theta.data_ptr<double>(),
+                               var.data_ptr<double>(), log_prior.data_ptr<double>(), slab.data_ptr<double>(),
+                               out.data_ptr<double>(), (int)N, (int)T, (int)F, cur_stream(real));
+  return out;
+}
+
+Tensor lp_cols(Tensor a, Tensor b) {
+  CHECK_F32(a); CHECK_F32(b);
+  TORCH_CHECK(a.dim() == 2 && a.sizes() == b.sizes() && a.device() == b.device(),
+              "lp_cols: a and b must be (n, F) on one device");
+  const int64_t n = a.size(0), F = a.size(1);
+  TORCH_CHECK(n >= 1 && n <= INT32_MAX && F >= 1 && F <= (1 << 20), "lp_cols: 1 <= n < 2^31, 1 <= F <= 2^20");
+  GUARD(a);
+  const auto f64 = a.options().dtype(at::kDouble);
+  Tensor out = out_empty({3, F}, f64);
+  Tensor slab = out_empty({(int64_t)hfrep::lp_blocks(n), 3, F}, f64);
+  hfrep::launch_lp_cols(a.data_ptr<float>(), b.data_ptr<float>(), slab.data_ptr<double>(), out.data_ptr<double>(), n,
+                        (int)F, cur_stream(a));
+  return out;
+}
+
 // ------------------------------------------------------------------------------------ p2p all-reduce
 // The buffer is a uint8 tensor over the hipExtMallocWithFlags allocation (freed by its deleter);
 // its data_ptr is the allocation base, which is what an IPC handle names.
@@ -1120,6 +1198,10 @@ TORCH_LIBRARY(hfrep, m) {
   m.def("step_advance_(Tensor(a!) step, Tensor(b!)? m_cache, float b1) -> ()");
   m.def("clip_(Tensor(a!) p, float c) -> ()");
   m.def("wdist_sorted(Tensor x, Tensor ref_sorted) -> Tensor");
+  m.def("ks_stat(Tensor x, Tensor ref_sorted) -> Tensor");
+  m.def("acf_mean(Tensor x, int nlags) -> Tensor");
+  m.def("nb_divergences(Tensor real, Tensor fake, Tensor theta, Tensor var, Tensor log_prior) -> Tensor");
+  m.def("lp_cols(Tensor a, Tensor b) -> Tensor");
   m.def("p2p_buffer(int cap, int device) -> Tensor", &p2p_buffer);  // no tensor inputs: catch-all kernel
   m.def("p2p_handle(Tensor buf) -> int[]");
   m.def("p2p_open(int[] handle, int device) -> int", &p2p_open);
@@ -1178,4 +1260,8 @@ TORCH_LIBRARY_IMPL(hfrep, CUDA, m) {
   m.impl("step_advance_", &step_advance_);
   m.impl("clip_", &clip_);
   m.impl("wdist_sorted", &wdist_sorted);
+  m.impl("ks_stat", &ks_stat);
+  m.impl("acf_mean", &acf_mean);
+  m.impl("nb_divergences", &nb_divergences);
+  m.impl("lp_cols", &lp_cols);
 }

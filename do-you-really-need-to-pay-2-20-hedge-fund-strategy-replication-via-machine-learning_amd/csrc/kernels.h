@@ -223,6 +223,29 @@ int wdist_blocks(int n);
 void launch_wdist_sorted(int dt, const void* x, const float* ref_sorted, uint32_t* ws, double* slab, double* out, int n,
                          int F, hipStream_t s);
 
+// ---- evalm.hip: GAN_eval's KS, ACF, Lp and naive-Bayes divergence metrics.  fp32 inputs, float64 sums,
+//      fixed-order reductions (no atomics: deterministic), every slab element written. ----
+// out (F): max |ECDF_x - ECDF_ref| per column of x (n, F) against the ascending rows of ref_sorted (F, n);
+// NaN where either column holds a NaN.  ws, ws2: F n keys each (ws2 unused, may be null, for n <= 16384: one
+// sorted chunk needs no merge pass), slab: F 2 ks_blocks(n) doubles.  n <= 2^24, F <= 1024 (the binding checks).
+int ks_blocks(int n);
+void launch_ks_stat(const float* x, const float* ref_sorted, uint32_t* ws, uint32_t* ws2, double* slab, double* out,
+                    int n, int F, hipStream_t s);
+// out (F, nlags + 1): the mean over n of the autocorrelations of x[n, :, f] (demeaned, divided by lag 0).
+// slab: acf_blocks(N) (nlags + 1) F doubles.  acf_supported: the window and the accumulators fit the LDS.
+bool acf_supported(int T, int F, int nlags);
+int acf_blocks(int N);
+void launch_acf_mean(const float* x, double* slab, double* out, int N, int T, int F, int nlags, hipStream_t s);
+// out (4): sum KL, sum sqrt KL, sum JS, sum sqrt JS over the N F series pairs of real / fake (N, T, F), from
+// the Gaussian naive-Bayes posteriors of theta, var (F, T) and log_prior (F).  slab: nb_slab_rows(N) 4 doubles.
+bool nb_supported(int T, int F);  // F <= 64, T <= 168
+int nb_slab_rows(int N);
+void launch_nb_divergences(const float* real, const float* fake, const double* theta, const double* var,
+                           const double* log_prior, double* slab, double* out, int N, int T, int F, hipStream_t s);
+// out (3, F): sum |d|, sum d^2, max |d| per column of d = a - b (n, F).  slab: lp_blocks(n) 3 F doubles.
+int lp_blocks(int64_t n);
+void launch_lp_cols(const float* a, const float* b, double* slab, double* out, int64_t n, int F, hipStream_t s);
+
 // ---- p2p.hip: one-shot all-reduce over IPC-mapped peer buffers (layout in p2p.hip) ----
 constexpr int kP2PMaxRanks = 8, kP2PMaxBlocks = 256;
 constexpr int kP2PCtr = 0, kP2PDone = 128, kP2PErr = 256, kP2PFlags = 4096, kP2PData = 16384;

@@ -341,6 +341,55 @@ def wdist_ref(real: torch.Tensor) -> torch.Tensor:
     return torch.sort(real.to(torch.float32).t().contiguous(), dim=1).values.contiguous()
 
 
+# GAN_eval's KS, ACF, Lp and naive-Bayes divergence metrics (csrc/evalm.hip): contiguous fp32 inputs, float64
+# results, fixed-order reductions (bitwise reproducible), stream-ordered, no host synchronise
+KS_MAX_ROWS = 1 << 24  # ks_stat's largest sample on the GPU (two F n key workspaces)
+
+
+def ks_stat(x: torch.Tensor, ref_sorted: torch.Tensor) -> torch.Tensor:
+    """(F,) float64: the two-sample KS statistic of every column of x (n, F) against the fixed sample
+    ``ref_sorted = wdist_ref(real)`` (F, n).  n <= 2^24 on the GPU.  Contract: :func:`reference.ks_stat`."""
+    if _nat(x):
+        return _ops().ks_stat(x, ref_sorted)
+    return R.ks_stat(x, ref_sorted)
+
+
+def acf_mean(x: torch.Tensor, nlags: int = 17) -> torch.Tensor:
+    """(F, nlags + 1) float64: the autocorrelations of x[n, :, f] (N, T, F) averaged over n.  On the GPU the
+    window and the accumulators must fit the LDS (:func:`acf_mean_supported`).  Contract:
+    :func:`reference.acf_mean`."""
+    if _nat(x):
+        return _ops().acf_mean(x, int(nlags))
+    return R.acf_mean(x, int(nlags))
+
+
+def acf_mean_supported(T: int, F: int, nlags: int) -> bool:
+    """The native acf_mean's LDS plan: T F floats and (nlags + 3) F doubles within 160 KB."""
+    return 0 <= nlags <= 4096 and 4 * T * F + 8 * (nlags + 3) * F <= 160 * 1024
+
+
+def nb_divergences(real: torch.Tensor, fake: torch.Tensor, theta: torch.Tensor, var: torch.Tensor,
+                   log_prior: torch.Tensor) -> torch.Tensor:
+    """(4,) float64: sum KL, sum sqrt KL, sum JS, sum sqrt JS of the Gaussian-naive-Bayes posteriors of the
+    paired series of real / fake (N, T, F); theta, var (F, T) and log_prior (F,) float64.  On the GPU F <= 64
+    and T <= 168 (:func:`nb_divergences_supported`).  Contract: :func:`reference.nb_divergences`."""
+    if _nat(real):
+        return _ops().nb_divergences(real, fake, theta, var, log_prior)
+    return R.nb_divergences(real, fake, theta, var, log_prior)
+
+
+def nb_divergences_supported(T: int, F: int) -> bool:
+    return 1 <= F <= 64 and 1 <= T <= 168
+
+
+def lp_cols(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """(3, F) float64: sum |d|, sum d^2, max |d| per column of d = a - b (n, F).  Contract:
+    :func:`reference.lp_cols`."""
+    if _nat(a):
+        return _ops().lp_cols(a, b)
+    return R.lp_cols(a, b)
+
+
 def interpolate(real: torch.Tensor, fake: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
     """alpha (B,) per-sample: alpha*real + (1-alpha)*fake (GAN/MTSS_WGAN_GP.py:197-199)."""
     if _nat(real):

@@ -202,6 +202,77 @@ def wdist_sorted(x: torch.Tensor, ref_sorted: torch.Tensor) -> torch.Tensor:
     return torch.cat([w, w.mean().reshape(1)])
 
 
+def ks_stat(x: torch.Tensor, ref_sorted: torch.Tensor) -> torch.Tensor:
+    """(F,) float64: the two-sample Kolmogorov-Smirnov statistic of every column of x (n, F) against the
+    sample whose ascending columns are the rows of ref_sorted (F, n): the largest |ECDF_x - ECDF_ref| over
+    every pooled point, right-continuous ECDFs (``scipy.stats.kstest(a, b).statistic``; an integer count
+    difference divided by n, so exact).  +-inf are ordinary values; a NaN in either column makes that
+    column's statistic NaN, which is what scipy's default ``nan_policy='propagate'`` returns."""
+    n = x.shape[0]
+    xs = torch.sort(x.to(torch.float64).t().contiguous(), dim=1).values
+    rs = ref_sorted.to(torch.float64).contiguous()
+    bad = torch.isnan(xs).any(dim=1) | torch.isnan(rs).any(dim=1)
+    pts = torch.cat([xs, rs], dim=1)
+    cx = torch.searchsorted(xs, pts, right=True)
+    cr = torch.searchsorted(rs, pts, right=True)
+    d = (cx - cr).abs().max(dim=1).values.to(torch.float64) / n
+    return torch.where(bad, torch.full_like(d, float("nan")), d)
+
+
+def acf_mean(x: torch.Tensor, nlags: int = 17) -> torch.Tensor:
+    """(F, nlags + 1) float64: the mean over n of the sample autocorrelations of the series x[n, :, f]
+    (demeaned over T, lag k = sum_t d_t d_{t+k} / sum_t d_t^2; NaN for k >= T and for a constant series):
+    ``acf_batch(x.transpose(0, 2, 1), nlags).mean(axis=0)`` of hfrep.eval.gan_eval."""
+    xt = x.to(torch.float64).permute(0, 2, 1)
+    xt = xt - xt.mean(dim=-1, keepdim=True)
+    T = xt.shape[-1]
+    den = (xt * xt).sum(dim=-1)
+    out = torch.full(xt.shape[:-1] + (nlags + 1,), float("nan"), dtype=torch.float64, device=x.device)
+    for k in range(min(nlags + 1, T)):
+        out[..., k] = (xt[..., : T - k] * xt[..., k:]).sum(dim=-1) / den
+    return out.mean(dim=0)
+
+
+def _rel_entr(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """``scipy.special.rel_entr``: x log(x / y) for x, y > 0; 0 for x == 0 <= y; +inf otherwise; NaN kept."""
+    pos = (x > 0) & (y > 0)
+    one = torch.ones_like(x)
+    v = torch.where(pos, x, one) * torch.log(torch.where(pos, x, one) / torch.where(pos, y, one))
+    out = torch.where(pos, v, torch.where((x == 0) & (y >= 0), torch.zeros_like(x), torch.full_like(x, float("inf"))))
+    return torch.where(torch.isnan(x) | torch.isnan(y), x + y, out)
+
+
+def nb_divergences(real: torch.Tensor, fake: torch.Tensor, theta: torch.Tensor, var: torch.Tensor,
+                   log_prior: torch.Tensor) -> torch.Tensor:
+    """(4,) float64: [sum KL, sum sqrt KL, sum JS, sum sqrt JS] over the N F series pairs (real[n, :, f],
+    fake[n, :, f]) of the (N, T, F) windows, from the posteriors of a fitted Gaussian naive Bayes
+    (theta, var (C, T) with sklearn's ``epsilon_`` in var, log_prior (C,)): sklearn's joint log likelihood
+    ``log_prior_c - 1/2 sum_t log(2 pi var_ct) - 1/2 sum_t (x_t - theta_ct)^2 / var_ct``, posteriors
+    ``exp(jll - logsumexp(jll))``, KL = sum_c rel_entr(p_fake, p_real) and JS = 1/2 sum_c rel_entr(p_fake, m)
+    + 1/2 sum_c rel_entr(p_real, m) with m = (p_fake + p_real) / 2 (GAN_eval.kl_div / js_div before the mean)."""
+    th, va, lp = theta.to(torch.float64), var.to(torch.float64), log_prior.to(torch.float64)
+    base = lp - 0.5 * torch.log(2.0 * torch.pi * va).sum(dim=1)
+
+    def post(a):
+        rows = a.to(torch.float64).permute(0, 2, 1).reshape(-1, a.shape[1])
+        jll = base[None, :] - 0.5 * (((rows[:, None, :] - th[None]) ** 2) / va[None]).sum(dim=2)
+        return torch.exp(jll - torch.logsumexp(jll, dim=1, keepdim=True))
+
+    pr, pf = post(real), post(fake)
+    m = 0.5 * (pf + pr)
+    kl = _rel_entr(pf, pr).sum(dim=1)
+    js = 0.5 * _rel_entr(pf, m).sum(dim=1) + 0.5 * _rel_entr(pr, m).sum(dim=1)
+    return torch.stack([kl.sum(), torch.sqrt(kl).sum(), js.sum(), torch.sqrt(js).sum()])
+
+
+def lp_cols(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """(3, F) float64: sum |d|, sum d^2 and max |d| of every column of d = a - b (n, F), the difference
+    formed in float64: the 1-, 2- (squared) and inf-norms ``GAN_eval.lp_dist`` divides by n."""
+    d = (a.to(torch.float64) - b.to(torch.float64)).abs()
+    mx = torch.where(torch.isnan(d).any(dim=0), torch.full_like(d[0], float("nan")), d.max(dim=0).values)
+    return torch.stack([d.sum(dim=0), (d * d).sum(dim=0), mx])
+
+
 # ======================================================================================
 # 2. explicit primitives (contracts of the native kernels)
 # ======================================================================================
