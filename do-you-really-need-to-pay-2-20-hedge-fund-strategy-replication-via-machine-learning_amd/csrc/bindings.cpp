@@ -189,7 +189,8 @@ void lstm_wgrad_(Tensor x, Tensor hs, Tensor dZ, Tensor gW, Tensor gU, optional<
   const void* D1 = tangent ? dZd->data_ptr() : nullptr;
   float* gbp = gb.has_value() ? gb->data_ptr<float>() : nullptr;
   if (f32) {
-    // impl (fp32): 0 = default, 1 = exact-fp32 MFMA kernel, 2 = three-term bf16 split kernel
+    // impl (fp32): 0 = default, 1 = exact-fp32 MFMA kernel, 2 / 3 = three-term bf16 split kernel (pair / quad),
+    // 4 = the split kernel with MFMA and staging wave roles (kernels.h)
     Tensor ws = out_empty({(int64_t)hfrep::lstmf_wgrad_workspace_floats(M, K, (int)impl)}, x.options());
     hfrep::launch_lstmf_wgrad(x.data_ptr(), hs.data_ptr(), dZ.data_ptr(),
                               X1, H1, D1, gW.data_ptr<float>(), gU.data_ptr<float>(), gbp,

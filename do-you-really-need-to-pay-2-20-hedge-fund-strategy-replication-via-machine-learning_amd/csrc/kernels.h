@@ -71,8 +71,10 @@ bool launch_lstmf_tbwd(const float* dH, const float* dHd, const float* tape, con
 // gU += Hprev^T dZ (+ Hdprev^T dZd), gb += colsum dZ, through per-workgroup slabs in ws
 // (lstmf_wgrad_workspace_floats) and one fixed-order reduce
 bool lstmf_wgrad_supported(int K, int H, int N);
-// impl: 0 = default (exact under HFREP_FP32_EXACT=1, else the pair split for K <= 36 and the quad split for K = 100), 1 = exact-fp32
-// MFMA, 2 = the three-term bf16 split (pair), 3 = the three-term bf16 split (quad)
+// impl: 0 = default (exact under HFREP_FP32_EXACT=1, else the role-split kernel for fp32 operands at K in {32, 100}, the pair split
+// for K = 35 / 36 and the pair / quad split for FP3-plane operands at K = 32 / 100), 1 = exact-fp32 MFMA, 2 = the three-term bf16
+// split (pair), 3 = the three-term bf16 split (quad), 4 = the three-term bf16 split with MFMA and staging wave roles (fp32 operands,
+// K in {32, 100}: bitwise equal to impl 2 / 3 there; any other case runs as the default)
 size_t lstmf_wgrad_workspace_floats(int M, int K, int impl = 0);
 bool launch_lstmf_wgrad(const void* X, const void* Hs, const void* D, const void* Xd, const void* Hds, const void* Dd,
                         float* gW, float* gU, float* gb, int M, int K, int Tn, float* ws, hipStream_t s, int impl = 0,

@@ -1984,6 +1984,303 @@ lstmf_wgrad_q4_kernel(const void* __restrict__ X, const void* __restrict__ Hs, c
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// split weight gradient, MFMA and staging ROLES: lstmf_wgrad_roles_kernel
+// ------------------------------------------------------------------------------------------
+// lstmf_wgrad_split_kernel and lstmf_wgrad_q4_kernel run eight identical waves: each reads its A
+// fragments from LDS, issues the MFMA chains, adds the fresh accumulators in VALU and runs its slice
+// of the next chunk's staging (global loads, split3, LDS stores).  A wave issues in order and there
+// are two per SIMD, so LDS latency, MFMA result latency and the staging VALU alternate instead of
+// overlapping (31 - 38 % MFMA busy, about twice the kernels' own issue bound), and both kernels sit at
+// the 256-register cap with spills.  Here the two jobs go to different waves that share a SIMD, as in
+// lstmf_bwdp_kernel: waves 0-3 are MFMA waves, waves 4-7 staging waves (the waves of a workgroup go
+// round the SIMDs, so every SIMD hosts one of each).
+//   staging waves: every global access.  Chunk c + 2's fp32 rows are loaded at the top of chunk c (two
+//     register sets alternate), then chunk c + 1's rows are split and stored into LDS buffer S ^ 1.
+//   MFMA waves: no global memory instruction, their only waits are on LDS.  Wave w owns the tiles
+//     [ts(w), ts(w + 1)) of the j-major list L = j NI + i (23 / 23 / 23 / 22 of 13 x 7 at K = 100,
+//     30 / 29 / 29 / 29 of 9 x 13 at K = 32), keeps the D fragments of its <= 4 j-tiles for the chunk
+//     and walks its tiles i-major with the A fragments one i-tile ahead: every operand is read from LDS
+//     once per wave.  Two fresh accumulators alternate, and tile n's VALU add is issued after tile
+//     n + 1's MFMAs, so no MFMA result wait is exposed.
+// One workgroup barrier per chunk separates "buffer S consumed" from "buffer S ^ 1 produced".  The role
+// branch is taken once, outside the chunk loop; each role's chunk body is straight-line code.
+// Arithmetic, workgroup partition (column pair of 208 for K <= 36, column quad of 100 above), row
+// ranges, slab and LDS images are those of the pair / quad kernel: a tile's six products go in the same
+// order into a zeroed accumulator that is added to the running sum once per chunk, so the result is
+// bitwise that of lstmf_wgrad_split_kernel (K = 32) / lstmf_wgrad_q4_kernel (K = 100).
+#ifndef HFREP_WGRAD_ROLES_APF
+#define HFREP_WGRAD_ROLES_APF 1  // i-tiles of lead of the MFMA waves' A-fragment reads (A/B: docs/PERF.md)
+#endif
+#ifndef HFREP_WGRAD_ROLES_PRIO
+#define HFREP_WGRAD_ROLES_PRIO 0  // 1: the MFMA waves at priority 1 for the chunk loop (A/B: docs/PERF.md)
+#endif
+template <int KX>
+struct WRGeo {
+  static constexpr bool QUAD = KX > 36;
+  static constexpr int NP = QUAD ? 4 : 2;                   // column parts per row range
+  static constexpr int CDP = QUAD ? WQ_CD : WS_CD;          // D columns per part
+  static constexpr int NJ = (CDP + 15) / 16;                // j-tiles per part
+  static constexpr int KR = KX + FH + 1;
+  static constexpr int NI = (KR + 15) / 16;
+  static constexpr int NT = NI * NJ;                        // output tiles per workgroup
+  static constexpr int ts(int w) { return w * (NT / 4) + (w < NT % 4 ? w : NT % 4); }  // first tile of MFMA wave w
+  static constexpr int MAXT = (NT + 3) / 4;
+  static constexpr int ND4 = CDP / 4;                       // float4 per D image row
+  static constexpr int JX = (32 * KX / 4 + 255) / 256, JH = (32 * FH / 4 + 255) / 256, JD = (32 * ND4 + 255) / 256;
+  static constexpr int NS = JX + JH + JD;                   // float4 staging slots per staging lane
+  static_assert(KX % 4 == 0 && CDP % 4 == 0 && 16 * NI <= WS_CA && MAXT * 4 <= 120, "wgrad roles: K");
+  using Img = WImg<16 * NI, 16 * NJ>;
+};
+
+template <int KX>
+__global__ void __launch_bounds__(512, 1)
+lstmf_wgrad_roles_kernel(const float* __restrict__ X, const float* __restrict__ Hs, const float* __restrict__ D,
+                         const float* __restrict__ Xd, const float* __restrict__ Hds, const float* __restrict__ Dd,
+                         float* __restrict__ slab, int M, int Tn, int rows_per_z, int Z) {
+  using G = WRGeo<KX>;
+  using GI = typename G::Img;
+  constexpr int NI = G::NI, NP = G::NP, JX = G::JX, JH = G::JH, NS = G::NS;
+  constexpr int XRB = 4 * KX, HRB = 4 * FH, DRB = 4 * FG;  // row bytes
+  extern __shared__ __attribute__((aligned(16))) char wsm_[];
+  lds_char* wsm = (lds_char*)wsm_;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // block -> (row range z, column part jp); with Z % 8 == 0 the parts of a row range share an XCD
+  int z, jp;
+  if (Z % 8 == 0) {
+    const int slot = blockIdx.x >> 3;
+    jp = slot % NP;
+    z = (slot / NP) * 8 + (blockIdx.x & 7);
+  } else {
+    jp = blockIdx.x % NP;
+    z = blockIdx.x / NP;
+  }
+  const int mb = z * rows_per_z, me = min(M, mb + rows_per_z);
+  const int jbase = G::CDP * jp, ncol = min(G::CDP, FG - jbase);  // real D columns of this part
+  const int nr = me > mb ? me - mb : 0, nch = (nr + 31) / 32;
+  const int nseg = Xd ? 2 : 1;
+
+  // zero both buffers (pad columns, the zero j-tile of the last pair part)
+  for (int i = tid; i < 2 * GI::BUF / 16; i += 512) reinterpret_cast<__attribute__((address_space(3))) u32x4_t*>(wsm)[i] = u32x4_t{0, 0, 0, 0};
+  __syncthreads();
+
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  // barriers per segment, both roles: one after the prologue (buffer 0 and the bias column staged), one
+  // per chunk
+  if (w < 4) {
+    // ---------------- MFMA role ----------------
+    auto role = [&](auto WK) {
+      constexpr int W = decltype(WK)::value;
+      constexpr int TS = G::ts(W), TE = G::ts(W + 1), JA = TS / NI, NJW = (TE - 1) / NI - JA + 1;
+      f32x4 acc[TE - TS];
+#pragma unroll
+      for (int a = 0; a < TE - TS; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+      // per-buffer lane bases of the transposed reads (A image, D image), opaque to the compiler: with
+      // the buffer and image offsets folded into the reads' immediates they overflowed the 16-bit field
+      int tro_a[2], tro_d[2];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        tro_a[b] = tr_lane_off(lane, GI::ROWA) + b * GI::BUF;
+        tro_d[b] = tr_lane_off(lane, GI::ROWD) + b * GI::BUF + GI::IMGD;
+        asm volatile("" : "+v"(tro_a[b]), "+v"(tro_d[b]));
+      }
+      auto chunk = [&](auto S_) {
+        constexpr int S = decltype(S_)::value;
+        bf16x8 bfr[NJW][3];
+#pragma unroll
+        for (int jj = 0; jj < NJW; ++jj)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) bfr[jj][q] = tr_frag<GI::ROWD>(wsm + q * GI::PLD, tro_d[S], 16 * (JA + jj));
+        constexpr int PF = HFREP_WGRAD_ROLES_APF;  // A fragments PF i-tiles ahead, PF + 1 sets
+        bf16x8 af[PF + 1][3];
+#pragma unroll
+        for (int i = 0; i < PF; ++i)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) af[i][q] = tr_frag<GI::ROWA>(wsm + q * GI::PLA, tro_a[S], 16 * i);
+        f32x4 t[2];
+        int pend = -1, par = 0;  // (compile-time after unrolling) tile whose add is outstanding, fresh set
+#pragma unroll
+        for (int ii = 0; ii < NI; ++ii) {
+          __builtin_amdgcn_sched_barrier(0);
+          if (ii + PF < NI) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) af[(ii + PF) % (PF + 1)][q] = tr_frag<GI::ROWA>(wsm + q * GI::PLA, tro_a[S], 16 * (ii + PF));
+          }
+          __builtin_amdgcn_sched_barrier(0);  // (the prefetch ahead of this i-tile's MFMAs: a full i-tile of lead)
+          const bf16x8(&a3)[3] = af[ii % (PF + 1)];
+#pragma unroll
+          for (int jj = 0; jj < NJW; ++jj) {
+            const int L = (JA + jj) * NI + ii;
+            if (L < TS || L >= TE) continue;  // (compile-time)
+            f32x4 u = mma32(a3[2], bfr[jj][0], f32x4{0.f, 0.f, 0.f, 0.f});  // lh
+            u = mma32(a3[0], bfr[jj][2], u);                                 // hl
+            u = mma32(a3[1], bfr[jj][1], u);                                 // mm
+            u = mma32(a3[1], bfr[jj][0], u);                                 // mh
+            u = mma32(a3[0], bfr[jj][1], u);                                 // hm
+            u = mma32(a3[0], bfr[jj][0], u);                                 // hh
+            t[par] = u;
+            __builtin_amdgcn_sched_barrier(0);
+            if (pend >= 0) acc[pend] += t[par ^ 1];  // the previous tile's add, behind this tile's MFMAs
+            pend = L - TS;
+            par ^= 1;
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        acc[pend] += t[par ^ 1];
+      };
+#if HFREP_WGRAD_ROLES_PRIO
+      __builtin_amdgcn_s_setprio(1);
+#endif
+      for (int seg = 0; seg < nseg; ++seg) {
+        lds_barrier();
+        int c = 0;
+        for (; c + 1 < nch; c += 2) {
+          chunk(I0{});
+          lds_barrier();
+          chunk(I1{});
+          lds_barrier();
+        }
+        if (c < nch) {
+          chunk(I0{});
+          lds_barrier();
+        }
+      }
+      // slab store: tile L = TS + n -> C[16 i + 4 g + r][jbase + 16 j + c16]
+      float* out = slab + (size_t)z * G::KR * FG;
+      const int g = lane >> 4, c16 = lane & 15;
+#pragma unroll
+      for (int n = 0; n < TE - TS; ++n) {
+        const int i = (TS + n) % NI, j = (TS + n) / NI;
+        const int col = 16 * j + c16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * i + 4 * g + r;
+          if (row < G::KR && col < ncol) out[(size_t)row * FG + jbase + col] = acc[n][r];
+        }
+      }
+    };
+    switch (w) {
+      case 0: role(std::integral_constant<int, 0>{}); break;
+      case 1: role(std::integral_constant<int, 1>{}); break;
+      case 2: role(std::integral_constant<int, 2>{}); break;
+      default: role(std::integral_constant<int, 3>{}); break;
+    }
+  } else {
+    // ---------------- staging role ----------------
+    const int st = tid - 256;
+    // float4 slot s of this lane in a 32-row chunk: X (JX slots), H (JH), D (JD); element e = lane' +
+    // 256 j of the kind's row-major list, the lane index rotated by a wave per kind so the ragged last
+    // slots of the three kinds fall on different waves.  gv: byte offset in the chunk frame (kOOB:
+    // none), lo: LDS byte offset (-1: none), rr: chunk row
+    int gv[NS], lo[NS], rr[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (s < JX) {
+        const int e = st + 256 * s, r = e / (KX / 4), c4 = e - r * (KX / 4);
+        const bool ok = e < 32 * KX / 4;
+        gv[s] = ok ? r * XRB + 16 * c4 : kOOB;
+        lo[s] = ok ? r * GI::ROWA + 8 * c4 : -1;
+        rr[s] = ok ? r : 0;
+      } else if (s < JX + JH) {
+        const int e = ((st + 64) & 255) + 256 * (s - JX), r = e / (FH / 4), c4 = e - r * (FH / 4);
+        const bool ok = e < 32 * FH / 4;
+        gv[s] = ok ? r * HRB + 16 * c4 : kOOB;
+        lo[s] = ok ? r * GI::ROWA + 2 * KX + 8 * c4 : -1;
+        rr[s] = ok ? r : 0;
+      } else {
+        const int e = ((st + 128) & 255) + 256 * (s - JX - JH), r = e / G::ND4, c4 = e - r * G::ND4;
+        const bool ok = e < 32 * G::ND4 && 4 * c4 < ncol;
+        gv[s] = ok ? r * DRB + 16 * c4 : kOOB;
+        lo[s] = ok ? GI::IMGD + r * GI::ROWD + 8 * c4 : -1;
+        rr[s] = ok ? r : 0;
+      }
+    }
+    const int step32 = 32 % Tn;
+    f32x4 v[2][NS];
+    for (int seg = 0; seg < nseg; ++seg) {
+      const char* Xs = reinterpret_cast<const char*>(seg ? Xd : X);
+      const char* Hq = reinterpret_cast<const char*>(seg ? Hds : Hs);
+      const char* Dq = reinterpret_cast<const char*>(seg ? Dd : D);
+      // per-workgroup descriptors (a whole-tensor one wraps past 4 GiB of dZ).  The H descriptor starts
+      // at row mb - 1 (row -1 for mb = 0, whose h_{-1} is never addressed: the t = 0 rows are masked) so
+      // every voffset is >= 0 -- the range check is on voffset alone
+      const rsrc_t rx = make_rsrc(Xs + (size_t)mb * XRB, nr * XRB);
+      const rsrc_t rh = make_rsrc(Hq + ((ptrdiff_t)mb - 1) * HRB, (nr ? nr + 1 : 0) * HRB);
+      const rsrc_t rd = make_rsrc(Dq + (size_t)mb * DRB + jbase * 4, nr ? (nr - 1) * DRB + ncol * 4 : 0);
+      int tm[JH];  // (row mod Tn) of this lane's H slots at the next chunk to load
+#pragma unroll
+      for (int j = 0; j < JH; ++j) tm[j] = (mb + rr[JX + j]) % Tn;
+      // the chunk at row m0 into register set Q (rows past me read zeros: voffset out of range); an H
+      // slot's (row mod Tn) then advances to its next chunk
+      auto load = [&](auto Q_, int m0) {
+        constexpr int Q = decltype(Q_)::value;
+        const int lim = me - m0;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const bool in = rr[s] < lim;
+          if (s < JX) {
+            v[Q][s] = ld4s(rx, in ? gv[s] : kOOB, (m0 - mb) * XRB);
+          } else if (s < JX + JH) {
+            int& tmj = tm[s - JX];
+            v[Q][s] = ld4s(rh, in && tmj != 0 ? gv[s] : kOOB, (m0 - mb) * HRB);
+            tmj += step32;
+            if (tmj >= Tn) tmj -= Tn;
+          } else {
+            v[Q][s] = ld4s(rd, in ? gv[s] : kOOB, (m0 - mb) * DRB);
+          }
+        }
+      };
+      // register set Q split into the three planes of buffer `buf`
+      auto stage = [&](auto Q_, int buf) {
+        constexpr int Q = decltype(Q_)::value;
+        lds_char* base = wsm + buf * GI::BUF;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          if (lo[s] >= 0) {
+            uint32_t p[3][2];
+            split3(v[Q][s], p);
+            const int pl = s < JX + JH ? GI::PLA : GI::PLD;
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+              *reinterpret_cast<__attribute__((address_space(3))) u32x2_t*>(base + lo[s] + q * pl) = u32x2_t{p[q][0], p[q][1]};
+          }
+        }
+      };
+      // bias column KR - 1 of A: 1 in plane h for the primal segment, 0 for the tangent one.  (Every
+      // MFMA wave is past the last chunk's barrier of the previous segment: both buffers are idle.)
+      if (st < 64) {
+        const int buf = st >> 5, r = st & 31;
+        *reinterpret_cast<__attribute__((address_space(3))) uint16_t*>(wsm + buf * GI::BUF + r * GI::ROWA + (G::KR - 1) * 2) =
+            seg ? 0 : 0x3f80;
+      }
+      // prologue: chunk 0 staged into buffer 0, chunk 1 in flight in set 1
+      load(I0{}, mb);
+      stage(I0{}, 0);
+      load(I1{}, mb + 32);
+      lds_barrier();
+      // chunk c (S = c & 1): chunk c + 2's loads into set S (its rows went to buffer S during chunk
+      // c - 1), then set S ^ 1 (chunk c + 1) into buffer S ^ 1.  Unconditional: after the last chunk the
+      // (zero) rows past the range go to the idle buffer
+      int c = 0;
+      for (; c + 1 < nch; c += 2) {
+        load(I0{}, mb + 32 * (c + 2));
+        stage(I1{}, 1);
+        lds_barrier();
+        load(I1{}, mb + 32 * (c + 3));
+        stage(I0{}, 0);
+        lds_barrier();
+      }
+      if (c < nch) {
+        load(I0{}, mb + 32 * (c + 2));
+        stage(I1{}, 1);
+        lds_barrier();
+      }
+    }
+  }
+}
+
 constexpr int DS_KS = 13;  // the 400 gate columns as 13 k-steps of 32 (k = 400..415 zero)
 
 // ==========================================================================================
@@ -2967,10 +3264,11 @@ static int wgradf_grid(int M) {
 }
 bool lstmf_wgrad_supported(int K, int H, int N) { return H == FH && N == FG && (K == 32 || K == 35 || K == 36 || K == 100); }
 
-// impl 1 / 2 / 3: the exact-fp32 MFMA kernel / the three-term bf16 split (pair) / the split quad;
-// default (0): exact under HFREP_FP32_EXACT, else the pair split for K <= 36 (12.1 -> 9.8 ms at 12.6 M
-// rows), the quad for K = 100 (16.4 -> 15.3 ms; the pair kernel's 28-tile waves spill there: 52.8 ms;
-// profiles/r03_split)
+// impl 1 / 2 / 3 / 4: the exact-fp32 MFMA kernel / the three-term bf16 split (pair) / the split quad /
+// the split with MFMA and staging wave roles (pair partition at K = 32, quad partition at K = 100;
+// bitwise equal to impl 2 / 3 there); default (0): exact under HFREP_FP32_EXACT, else the role kernel for
+// fp32 operands at K in {32, 100}, the pair split for K = 35 / 36 and for FP3-plane operands at K = 32,
+// the quad for FP3-plane operands at K = 100 (profiles/r03_split, profiles/wgrad_roles)
 static int wgradf_version() { return fp32_exact() ? 1 : 0; }
 // split kernel: Z row ranges x 2 column halves, one workgroup per CU
 static int wgrads_z(int M) {
@@ -2982,24 +3280,44 @@ static int wgradq_z(int M) {
   const int chunks = (M + 31) / 32, q = device_cu_count() / 4;
   return chunks < q ? chunks : q;
 }
-static int wgradf_pick(int impl, int K, int M) {
+static int wgradf_pick(int impl, int K, int M, int pm = 0) {
   (void)M;
-  int v = impl >= 1 && impl <= 3 ? impl : wgradf_version();
+  int v = impl >= 1 && impl <= 4 ? impl : wgradf_version();
   if (K == 35 && v == 3) v = 2;  // the quad kernel reads 16-byte X rows only
+  const bool roles = (K == 32 || K == 100) && pm == 0;  // the role kernel: fp32 operands, K in {32, 100}
+  if (v == 0) v = roles ? 4 : 0;
+  if (v == 4 && !roles) v = 0;
   return v ? v : (K <= 36 ? 2 : 3);
 }
 size_t lstmf_wgrad_workspace_floats(int M, int K, int impl) {
+  // (the role kernel keeps the row ranges of the kernel it replaces: the pair's at K = 32, the quad's at 100)
   const int v = wgradf_pick(impl, K, M);
-  const int z = v == 1 ? wgradf_grid(M) : v == 3 ? wgradq_z(M) : wgrads_z(M);
+  const int z = v == 1 ? wgradf_grid(M) : v == 3 || (v == 4 && K == 100) ? wgradq_z(M) : wgrads_z(M);
   return (size_t)z * ((K == 35 ? 36 : K) + FH + 1) * FG;
 }
 
 bool launch_lstmf_wgrad(const void* X, const void* Hs, const void* D, const void* Xd, const void* Hds, const void* Dd,
                         float* gW, float* gU, float* gb, int M, int K, int Tn, float* ws, hipStream_t s, int impl, int pm) {
   if (!lstmf_wgrad_supported(K, FH, FG) || M <= 0) return false;
-  if (pm != 0 && (wgradf_pick(impl, K, M) == 1 || K == 35 || K == 36))
+  if (pm != 0 && (wgradf_pick(impl, K, M, pm) == 1 || K == 35 || K == 36))
     throw std::runtime_error("lstmf_wgrad: FP3-plane operands need the split kernels and K in {32, 100}");
-  if (wgradf_pick(impl, K, M) == 3) {
+  if (wgradf_pick(impl, K, M, pm) == 4) {
+    const bool quad = K == 100;
+    const int z0 = quad ? wgradq_z(M) : wgrads_z(M);
+    const int rpz = ((M + z0 - 1) / z0 + 31) / 32 * 32;
+    const int z = (M + rpz - 1) / rpz;
+    const float *Xf = static_cast<const float*>(X), *Hf = static_cast<const float*>(Hs), *Df = static_cast<const float*>(D);
+    const float *Xdf = static_cast<const float*>(Xd), *Hdf = static_cast<const float*>(Hds), *Ddf = static_cast<const float*>(Dd);
+    auto go = [&](auto k, int np, size_t sm) {
+      allow_lds(reinterpret_cast<const void*>(k));
+      hipLaunchKernelGGL(k, dim3(np * z), dim3(512), sm, s, Xf, Hf, Df, Xdf, Hdf, Ddf, ws, M, Tn, rpz, z);
+    };
+    if (quad) go(lstmf_wgrad_roles_kernel<100>, WRGeo<100>::NP, 2 * WRGeo<100>::Img::BUF);
+    else go(lstmf_wgrad_roles_kernel<32>, WRGeo<32>::NP, 2 * WRGeo<32>::Img::BUF);
+    launch_lstm_wgrad2_reduce(ws, gW, gU, gb, z, K, FH, FG, s);
+    return true;
+  }
+  if (wgradf_pick(impl, K, M, pm) == 3) {
     const int z0 = wgradq_z(M);
     const int rpz = ((M + z0 - 1) / z0 + 31) / 32 * 32;
     const int z = (M + rpz - 1) / rpz;
@@ -3017,7 +3335,7 @@ bool launch_lstmf_wgrad(const void* X, const void* Hs, const void* D, const void
     launch_lstm_wgrad2_reduce(ws, gW, gU, gb, z, K, FH, FG, s);
     return true;
   }
-  if (wgradf_pick(impl, K, M) != 1) {
+  if (wgradf_pick(impl, K, M, pm) != 1) {
     const int z0 = wgrads_z(M);
     const int rpz = ((M + z0 - 1) / z0 + 31) / 32 * 32;
     const int z = (M + rpz - 1) / rpz;

@@ -568,9 +568,11 @@ def lstm_wgrad_(x, hs, dZ, gW, gU, gb, xd=None, hds=None, dZd=None, impl: int = 
     shape is supported, csrc/gemm2.hip otherwise; ``impl=2`` forces the latter); fp32 GPU at the
     model widths (K in {32, 35, 36, 100}; 35-wide rows are read in place): ONE fused launch of
     csrc/lstm_f32.hip -- the fp32-accurate three-term bf16 split (every fp32 operand h + m + l, six
-    products on the bf16 matrix pipe): lstmf_wgrad_split_kernel for K <= 36 (``impl=2``),
-    lstmf_wgrad_q4_kernel for K = 100 (``impl=3``); the exact-fp32 MFMA kernel lstmf_wgrad_kernel
-    under HFREP_FP32_EXACT=1 (``impl=1``); otherwise per-product calls."""
+    products on the bf16 matrix pipe): lstmf_wgrad_roles_kernel (MFMA waves and staging waves,
+    ``impl=4``) for K in {32, 100}, lstmf_wgrad_split_kernel for K = 35 / 36 (``impl=2``: a column pair
+    per row range, the partition the role kernel keeps at K = 32 and matches bitwise);
+    lstmf_wgrad_q4_kernel (``impl=3``: a column quad, matched bitwise at K = 100); the exact-fp32 MFMA
+    kernel lstmf_wgrad_kernel under HFREP_FP32_EXACT=1 (``impl=1``); otherwise per-product calls."""
     f32 = (dZ.dtype == torch.float32 and x.shape[-1] in (32, 35, 36, 100) and hs.shape[-1] == 100
            and dZ.shape[-1] == 400)
     if (dZ.dtype == torch.bfloat16 or f32) and _nat(dZ):
