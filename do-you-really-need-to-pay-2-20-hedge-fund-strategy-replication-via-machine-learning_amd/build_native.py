@@ -62,11 +62,13 @@ def _flags():
     return kern, bind, link
 
 
-# per-translation-unit extra flags.  lstm_f32.hip: its split weight-gradient kernel runs one
-# straight-line body per wave kind behind a switch on the wave index; SimplifyCFG's common-code
+# per-translation-unit extra flags.  lstmf_grad.hip: its split weight-gradient kernels (pair, quad, roles)
+# run one straight-line body per wave kind behind a switch on the wave index; SimplifyCFG's common-code
 # sinking merged those bodies into one block with a run-time accumulator index, which moved the
-# accumulators to scratch memory (80 B per lane at K = 32)
-EXTRA_FLAGS = {"lstm_f32.hip": ["-mllvm", "-simplifycfg-sink-common=false"]}
+# accumulators to scratch memory (80 B per lane at K = 32).  lstm_f32.hip (the recurrent kernels, once
+# the same translation unit) keeps the flag so that its code generation stays what was measured.
+_NO_SINK = ["-mllvm", "-simplifycfg-sink-common=false"]
+EXTRA_FLAGS = {"lstmf_grad.hip": _NO_SINK, "lstm_f32.hip": _NO_SINK}
 
 
 def kernel_flags(src: str) -> list[str]:

@@ -39,9 +39,10 @@ void launch_lstm2_tbwd(const void* dH, const void* dHd, const void* tape, const 
                        hipStream_t s, const void* head_d = nullptr, const void* head_dd = nullptr,
                        const float* hw = nullptr);
 
-// ---- lstm_f32.hip (fp32, fused input projection, exact-fp32 MFMA; H == 100, K in {32, 35, 36, 100},
-//      act in {linear, sigmoid, tanh}; false = not supported).  Tapes: lane-native blocked fp32
-//      (lstmf_tape_elems floats; primal = gate activations + c, tangent = zdot + cdot). ----
+// ---- lstm_f32.hip (fp32 recurrent kernels: fused input projection, exact-fp32 MFMA or the three-term
+//      bf16 split; H == 100, K in {32, 35, 36, 100}, act in {linear, sigmoid, tanh}; false = not supported).
+//      Tapes: lane-native blocked fp32 (lstmf_tape_elems floats; primal = gate activations + c,
+//      tangent = zdot + cdot). ----
 bool lstmf_supported(int H, int K, int act);
 size_t lstmf_tape_elems(int B, int Tn);
 bool launch_lstmf_fwd(const float* x, const float* W, const float* b, const float* U, float* hs, float* tape, int B,
@@ -67,31 +68,27 @@ bool launch_lstmf_tbwd1(const float* dH, const float* aH, const float* tape, con
 bool launch_lstmf_tbwd(const float* dH, const float* dHd, const float* tape, const float* ttape, const float* U, float* dZ,
                        float* dZd, int B, int Tn, int H, int act, hipStream_t s, const float* hd = nullptr,
                        const float* hdd = nullptr, const float* hw = nullptr);
-// fused fp32 LSTM weight gradients (K in {32, 36, 100}, H = 100, N = 400): gW += X^T dZ (+ Xd^T dZd),
-// gU += Hprev^T dZ (+ Hdprev^T dZd), gb += colsum dZ, through per-workgroup slabs in ws
-// (lstmf_wgrad_workspace_floats) and one fixed-order reduce
-bool lstmf_wgrad_supported(int K, int H, int N);
-// impl: 0 = default (exact under HFREP_FP32_EXACT=1, else the role-split kernel for fp32 operands at K in {32, 100}, the pair split
-// for K = 35 / 36 and the pair / quad split for FP3-plane operands at K = 32 / 100), 1 = exact-fp32 MFMA, 2 = the three-term bf16
-// split (pair), 3 = the three-term bf16 split (quad), 4 = the three-term bf16 split with MFMA and staging wave roles (fp32 operands,
-// K in {32, 100}: bitwise equal to impl 2 / 3 there; any other case runs as the default)
-size_t lstmf_wgrad_workspace_floats(int M, int K, int impl = 0);
-bool launch_lstmf_wgrad(const void* X, const void* Hs, const void* D, const void* Xd, const void* Hds, const void* Dd,
-                        float* gW, float* gU, float* gb, int M, int K, int Tn, float* ws, hipStream_t s, int impl = 0,
-                        int pm = 0);  // pm: FP3-plane operands (bit 1 X, 2 H, 4 D interleaved)
-// fp32 input gradient X (M, KO) = D (M, N) W^T, W (KO, N) row-major; N = 400, KO <= 112
-bool lstmf_dgrad_supported(int N, int KO);
 // forward kernel selection: 1 = exact-fp32 everywhere, 2 = split recurrent product for K <= 36 (default);
 // returns the previous setting
 int set_lstmf_fwd_impl(int v);  // 1: exact-fp32 forward everywhere, 2: the split-recurrent one for K <= 36
 int set_lstmf_bwd_impl(int v);  // 2: the exact-fp32 BPTT kernel, 3: the split-recurrent one
+
+// ---- lstmf_grad.hip (fp32 LSTM gradient GEMMs; shared device helpers: lstmf_dev.h) ----
+// fused fp32 LSTM weight gradients (K in {32, 35, 36, 100}, H = 100, N = 400): gW += X^T dZ (+ Xd^T dZd),
+// gU += Hprev^T dZ (+ Hdprev^T dZd), gb += colsum dZ, through per-row-range slabs in ws
+// (lstmf_wgrad_workspace_floats) and one fixed-order reduce
+bool lstmf_wgrad_supported(int K, int H, int N);
+// impl: 0 = default (exact under HFREP_FP32_EXACT=1, else the role-split kernel at K in {32, 100} and the pair split for
+// K = 35 / 36), 1 = exact-fp32 MFMA, 2 = the three-term bf16 split (pair), 3 = the three-term bf16 split (quad; K = 35 runs
+// the pair), 4 = the three-term bf16 split with MFMA and staging wave roles (K in {32, 100}: bitwise equal to impl 2 / 3
+// there; any other K runs as the default)
+size_t lstmf_wgrad_workspace_floats(int M, int K, int impl = 0);
+bool launch_lstmf_wgrad(const float* X, const float* Hs, const float* D, const float* Xd, const float* Hds, const float* Dd,
+                        float* gW, float* gU, float* gb, int M, int K, int Tn, float* ws, hipStream_t s, int impl = 0);
+// fp32 input gradient X (M, KO) = D (M, N) W^T, W (KO, N) row-major; N = 400, KO <= 112
+bool lstmf_dgrad_supported(int N, int KO);
 // impl: 0 = default (exact under HFREP_FP32_EXACT=1, else the LDS-staged split for KO > 64), 1 = exact, 3 = three-term bf16 split
-bool launch_lstmf_dgrad(const void* D, const float* W, float* X, int M, int N, int KO, hipStream_t s, int impl = 0,
-                        bool pd = false);  // pd: dZ as FP3 planes (interleaved gate order)
-// FP3 planes (csrc/lstm_f32.hip): fp32 (M, C) <-> bf16 (M, 3, C) exact split planes; interleave: C = 400 in
-// the gate-interleaved column order k = 4 u + q
-void launch_fp3_split(const float* x, uint16_t* p, int64_t M, int C, bool interleave, hipStream_t s);
-void launch_fp3_join(const uint16_t* p, float* x, int64_t M, int C, bool interleave, hipStream_t s);
+bool launch_lstmf_dgrad(const float* D, const float* W, float* X, int M, int N, int KO, hipStream_t s, int impl = 0);
 
 // ---- ae.hip (factor autoencoder: the whole Keras fit -- MSE, Nadam, EarlyStopping -- in one launch) ----
 bool ae_fit_supported(int A, int k, int batch);

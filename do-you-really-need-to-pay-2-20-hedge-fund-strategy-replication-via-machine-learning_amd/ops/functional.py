@@ -95,7 +95,7 @@ def linear(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, act: int,
 
 
 # fp32 dZ (.., 400) @ W^T with W (K <= 112, 400): the LSTM layers' input gradient, on the native
-# kernels of csrc/lstm_f32.hip (lstmf_dgrad_s4 split / lstmf_dgrad exact)
+# kernels of csrc/lstmf_grad.hip (lstmf_dgrad_s4 split / lstmf_dgrad exact)
 
 
 def linear_dgrad(dz: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
@@ -567,7 +567,7 @@ def lstm_wgrad_(x, hs, dZ, gW, gU, gb, xd=None, hds=None, dZd=None, impl: int = 
     gb += sum(dZ).  bf16 GPU: ONE fused launch (csrc/wgrad3.hip LDS-DMA streaming kernel where the
     shape is supported, csrc/gemm2.hip otherwise; ``impl=2`` forces the latter); fp32 GPU at the
     model widths (K in {32, 35, 36, 100}; 35-wide rows are read in place): ONE fused launch of
-    csrc/lstm_f32.hip -- the fp32-accurate three-term bf16 split (every fp32 operand h + m + l, six
+    csrc/lstmf_grad.hip -- the fp32-accurate three-term bf16 split (every fp32 operand h + m + l, six
     products on the bf16 matrix pipe): lstmf_wgrad_roles_kernel (MFMA waves and staging waves,
     ``impl=4``) for K in {32, 100}, lstmf_wgrad_split_kernel for K = 35 / 36 (``impl=2``: a column pair
     per row range, the partition the role kernel keeps at K = 32 and matches bitwise);
