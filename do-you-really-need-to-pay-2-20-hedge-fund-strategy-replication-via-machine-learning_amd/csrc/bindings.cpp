@@ -452,6 +452,9 @@ std::tuple<Tensor, Tensor> lstmf_tbwd(optional<Tensor> dH, optional<Tensor> dHd,
   return {dZ, dZd};
 }
 
+// impl: 0 = default (exact under HFREP_FP32_EXACT, else the role kernel for KO > 64 and the exact kernel below),
+// 1 = exact-fp32 MFMA kernel, 3 = three-term bf16 split lstmf_dgrad_s4_kernel (the bitwise reference of the
+// tests), 4 = the split with MFMA / staging wave roles lstmf_dgrad_roles_kernel (bitwise equal to 3)
 Tensor lstmf_dgrad(Tensor dz, Tensor W, int64_t impl) {
   CHECK_F32(dz); CHECK_F32(W);
   TORCH_CHECK(dz.dim() == 2 && dz.is_contiguous() && W.dim() == 2 && W.is_contiguous() && W.size(1) == dz.size(1),

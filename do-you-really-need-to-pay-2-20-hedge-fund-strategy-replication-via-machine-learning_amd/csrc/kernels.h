@@ -87,7 +87,8 @@ bool launch_lstmf_wgrad(const float* X, const float* Hs, const float* D, const f
                         float* gW, float* gU, float* gb, int M, int K, int Tn, float* ws, hipStream_t s, int impl = 0);
 // fp32 input gradient X (M, KO) = D (M, N) W^T, W (KO, N) row-major; N = 400, KO <= 112
 bool lstmf_dgrad_supported(int N, int KO);
-// impl: 0 = default (exact under HFREP_FP32_EXACT=1, else the LDS-staged split for KO > 64), 1 = exact, 3 = three-term bf16 split
+// impl: 0 = default (exact under HFREP_FP32_EXACT=1, else the role-split kernel for KO > 64), 1 = exact, 3 = three-term
+// bf16 split (s4), 4 = the same split with MFMA / staging wave roles (bitwise equal to 3)
 bool launch_lstmf_dgrad(const float* D, const float* W, float* X, int M, int N, int KO, hipStream_t s, int impl = 0);
 
 // ---- ae.hip (factor autoencoder: the whole Keras fit -- MSE, Nadam, EarlyStopping -- in one launch) ----

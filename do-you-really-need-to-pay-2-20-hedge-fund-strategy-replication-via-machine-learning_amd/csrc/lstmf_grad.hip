@@ -1,7 +1,7 @@
 // fp32 LSTM gradient GEMMs (gfx950): the fused weight gradients -- exact fp32 (lstmf_wgrad_kernel) and the
 // three-term bf16 split as a column pair, a column quad and with MFMA / staging wave roles -- and the
-// input gradients dX = dZ W^T (lstmf_dgrad_kernel exact, lstmf_dgrad_s4_kernel split), with their
-// launchers.  The recurrent kernels (forwards, BPTTs, tangent reverses) are in lstm_f32.hip; what both
+// input gradients dX = dZ W^T (lstmf_dgrad_kernel exact, lstmf_dgrad_s4_kernel split, lstmf_dgrad_roles_kernel
+// the same split with MFMA / staging wave roles), with their launchers.  The recurrent kernels (forwards, BPTTs, tangent reverses) are in lstm_f32.hip; what both
 // files share is in lstmf_dev.h.
 #include "lstmf_dev.h"
 
@@ -1179,6 +1179,216 @@ lstmf_dgrad_s4_kernel(const float* __restrict__ D, const float* __restrict__ W, 
   if (c < nch) chunk(I0{}, c, 0);
 }
 
+// ------------------------------------------------------------------------------------------
+// the split input gradient with MFMA and staging wave roles: lstmf_dgrad_roles_kernel
+// ------------------------------------------------------------------------------------------
+// lstmf_dgrad_s4_kernel gives every wave every job in program order, one wave per SIMD: nothing covers a
+// wave's post-barrier A-fragment read, the MFMA drain before its output stores or its barrier wait, its
+// __syncthreads() drains the dZ prefetch and the output stores (vmcnt(0)) once per chunk, and at KO <= 112
+// wave 3's second tile is all padding (78 MFMAs per chunk on zero planes).  Here, as in
+// lstmf_wgrad_roles_kernel, the jobs go to different waves, 8 per workgroup, two per SIMD:
+//   MFMA waves 0..6: wave w owns the ONE output tile of columns 16 w .. 16 w + 15 for all 13 k-steps and
+//     holds its three W^T planes in registers (156 VGPRs; no AGPR pin).  Per chunk: the A fragments from
+//     the LDS image one k-step ahead, mma_split6 per k-step onto one accumulator that starts at zero, four
+//     dword stores.  The tile index is a run-time (uniform) value: every MFMA wave runs the same
+//     straight-line chunk body, columns >= KO store to kOOB.
+//   staging wave 7 (the slot of s4's padding tile): the dZ stream.  A 16-row chunk is 1600 contiguous
+//     float4 = 25 slots of 64 lanes.  The registers roll: slot j of the chunk due in the idle LDS buffer is
+//     split there and its registers are at once reloaded with slot j of the chunk DR_D chunks later, so
+//     DR_D whole chunks (25.6 KB each) per CU are always in flight.
+//   Alone the staging wave is the bound (25 slots x 26 instructions; as fast as s4, no faster), so each MFMA
+//     wave takes DR_SH of the 25 slots, each split between the MFMAs of one k-step, and the staging wave
+//     keeps 25 - 7 DR_SH.  At DR_SH = 2 every SIMD stages 12 - 13 slots beside its MFMAs (SIMD 3: one
+//     wave's 78 MFMAs and 2 + 11 slots; the others 156 MFMAs and 4 slots).  Measured at 6.3 M rows
+//     (profiles/dgrad_roles): DR_SH / DR_D = 0/1 3.44, 1/1 3.35, 2/1 3.15, 3/1 3.25, 1/2 3.15, 2/2 3.04,
+//     3/2 3.14 ms against s4's 3.46; the k-steps of the MFMA waves' slots and the staging wave at
+//     s_setprio 1 are neutral.
+// One lds_barrier() per chunk (LDS only: loads and stores stay in flight) separates "buffer P consumed"
+// from "buffer P ^ 1 produced"; the role branch is taken once, outside the chunk loop.  LDS image, per-chunk
+// descriptors from a 64-bit base (zero-size past M), chunk order (chunk i of workgroup b = b + i gridDim)
+// and the arithmetic per output element -- k-steps 0..12 in order, mma_split6's six products chained onto a
+// zero accumulator -- are those of s4: the result is bitwise that of lstmf_dgrad_s4_kernel.
+#ifndef HFREP_DGRAD_ROLES_SHARE
+#define HFREP_DGRAD_ROLES_SHARE 2  // DR_SH: staging slots (of 25) each MFMA wave takes, 0..3
+#endif
+#ifndef HFREP_DGRAD_ROLES_DEPTH
+#define HFREP_DGRAD_ROLES_DEPTH 2  // DR_D: register sets of the dZ stream = chunks in flight per CU, 1 or 2
+#endif
+constexpr int DR_SH = HFREP_DGRAD_ROLES_SHARE, DR_D = HFREP_DGRAD_ROLES_DEPTH;
+constexpr int DR_SLOTS = 16 * (FG / 4) / 64;  // 64-lane float4 slots per chunk (25)
+constexpr int DR_NS = DR_SLOTS - 7 * DR_SH;   // slots of the staging wave
+constexpr int DR_K0 = 2, DR_KST = 3;  // an MFMA wave's slot i goes between the MFMAs of k-step K0 + KST i
+static_assert(DR_SH >= 0 && DR_SH <= 3 && (DR_D == 1 || DR_D == 2), "dgrad roles: share / depth");
+
+__global__ void __launch_bounds__(512, 1)
+lstmf_dgrad_roles_kernel(const float* __restrict__ D, const float* __restrict__ W, float* __restrict__ X, int M, int KO) {
+  constexpr int DRB = 4 * FG;  // dZ row bytes
+  extern __shared__ __attribute__((aligned(16))) char drm_[];
+  lds_char* dsm = (lds_char*)drm_;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nch = (M + 15) / 16, cs = gridDim.x, cb = blockIdx.x;
+  // zero the k = 400..415 pad columns of both buffers (never staged; the k-step 12 fragments read them)
+  for (int i = tid; i < 2 * 3 * 16 * 2; i += 512) {
+    const int h = i & 1, b = i / 96, q = (i / 32) % 3, r = (i / 2) % 16;
+    *reinterpret_cast<__attribute__((address_space(3))) u32x4_t*>(dsm + b * DS4_BUF + q * DS4_PL +
+                                                                  (r * DS4_RS + FG + 8 * h) * 2) = u32x4_t{0, 0, 0, 0};
+  }
+  // chunk c's rows (past M: zero-size descriptor, zeros); slot s of a chunk: float4 e = lane + 64 s of its
+  // 1600, at byte 16 e of the chunk and at row e / 100, k = 4 (e % 100) of the image
+  auto drsrc = [&](int c) {
+    const int r0 = c * 16, nr = c < nch ? min(16, M - r0) : 0;
+    return make_rsrc(reinterpret_cast<const char*>(D) + (nr ? (size_t)r0 * DRB : 0), nr * DRB);
+  };
+  auto slot_lo = [&](int s) {
+    const int e = lane + 64 * s, r = e / 100;
+    return (r * DS4_RS + 4 * (e - 100 * r)) * 2;
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  if (w < 7) {
+    // ---------------- MFMA role ----------------
+    const int g = lane >> 4, c16 = lane & 15, col = 16 * w + c16;
+    // W^T planes of this wave's tile: B[k = 32 ks + 8 g + j][col] = W[col][k]
+    // (columns >= KO and k >= 400 read zeros: offsets out of range, no branch)
+    bf16x8 bw[DS_KS][3];
+    const rsrc_t rw = make_rsrc(W, KO * FG * 4);
+    int wrow = col * FG * 4;
+#pragma unroll
+    for (int ks = 0; ks < DS_KS; ++ks) {
+      // one k-step's loads and split at a time: the next k-step's offset is made to depend on this one's
+      // planes (all 26 loads hoisted ahead of the splits put the prologue past 256 registers)
+      if (ks) asm volatile("" : "+v"(wrow), "+v"(bw[ks - 1][0]), "+v"(bw[ks - 1][1]), "+v"(bw[ks - 1][2]));
+      const int k0 = 32 * ks + 8 * g, wo = col < KO && k0 < FG ? wrow + k0 * 4 : kOOB;
+      const f32x4 v0 = ld4(rw, wo), v1 = ld4(rw, wo == kOOB ? kOOB : wo + 16);
+      uint32_t p0[3][2], p1[3][2];
+      split3(v0, p0);
+      split3(v1, p1);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) bw[ks][q] = __builtin_bit_cast(bf16x8, make_uint4(p0[q][0], p0[q][1], p1[q][0], p1[q][1]));
+    }
+    const int ao = (c16 * DS4_RS + 8 * g) * 2;  // this lane's A fragment: row c16, k = 8 g .. + 7 of a k-step
+    // output rows 16 cc + 4 g + i, column 16 w + c16: byte offsets in the chunk's frame, kOOB for columns
+    // >= KO.  (Opaque to the compiler: re-deriving the select per chunk put a branch between the last MFMA
+    // and the stores of its result.)
+    int xo[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      xo[i] = col < KO ? ((4 * g + i) * KO + col) * 4 : kOOB;
+      asm volatile("" : "+v"(xo[i]));
+    }
+    // (share) this wave's DR_SH slots of the dZ stream: as the staging wave's, see below
+    constexpr int NX = DR_SH ? DR_SH : 1;
+    int xg[NX], xl[NX];
+    f32x4 vx[DR_D][NX];
+#pragma unroll
+    for (int i = 0; i < DR_SH; ++i) {
+      const int xs = DR_NS + DR_SH * w + i;
+      xg[i] = 16 * (lane + 64 * xs);
+      xl[i] = slot_lo(xs);
+    }
+#pragma unroll
+    for (int s = 0; s < DR_D; ++s) {
+      const rsrc_t rd = drsrc(cb + s * cs);
+#pragma unroll
+      for (int i = 0; i < DR_SH; ++i) vx[s][i] = ld4(rd, xg[i]);
+    }
+    {
+      const rsrc_t rd = drsrc(cb + DR_D * cs);
+#pragma unroll
+      for (int i = 0; i < DR_SH; ++i) {
+        split3_store(vx[0][i], dsm + xl[i], DS4_PL);
+        vx[0][i] = ld4(rd, xg[i]);
+      }
+    }
+    lds_barrier();
+    // chunk cc in buffer P; chunk cc + cs (register set S) goes to buffer P ^ 1
+    auto chunk = [&](auto P_, int cc) {
+      constexpr int P = decltype(P_)::value, Q = P ^ 1, S = Q % DR_D;
+      const lds_char* A_ = dsm + P * DS4_BUF + ao;
+      const rsrc_t rdn = drsrc(cc + (1 + DR_D) * cs);
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      // A fragments one k-step ahead (two sets): the LDS latency hides under the previous k-step's MFMAs
+      bf16x8 af[2][3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) af[0][q] = *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(A_ + q * DS4_PL);
+#pragma unroll
+      for (int ks = 0; ks < DS_KS; ++ks) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks + 1 < DS_KS) {
+#pragma unroll
+          for (int q = 0; q < 3; ++q)
+            af[(ks + 1) & 1][q] = *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(A_ + q * DS4_PL + 64 * (ks + 1));
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (the prefetch ahead of this k-step's MFMAs: a full k-step of lead)
+        acc = mma_split6(af[ks & 1], bw[ks], acc);
+        // slot i between the MFMAs of k-step DR_K0 + DR_KST i (in-order issue: the split's VALU only overlaps the
+        // matrix pipe there), its reload in the next k-step: ahead of the output stores (vmcnt is in order
+        // over loads and stores)
+#pragma unroll
+        for (int i = 0; i < DR_SH; ++i) {
+          if (ks == DR_K0 + DR_KST * i) {
+            split3_store(vx[S][i], dsm + Q * DS4_BUF + xl[i], DS4_PL);
+#pragma unroll
+            for (int n = 0; n < 6; ++n) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+            }
+          }
+          if (ks == DR_K0 + DR_KST * i + 1) vx[S][i] = ld4(rdn, xg[i]);
+        }
+      }
+      const int nr = min(16, M - 16 * cc);
+      const rsrc_t rx = make_rsrc(X + (size_t)16 * cc * KO, nr * KO * 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) st1(acc[i], rx, xo[i], 0);
+      lds_barrier();
+    };
+    for (int cc = cb;;) {
+      chunk(I0{}, cc);
+      if ((cc += cs) >= nch) break;
+      chunk(I1{}, cc);
+      if ((cc += cs) >= nch) break;
+    }
+  } else {
+    // ---------------- staging role ----------------
+    int lo[DR_NS];
+#pragma unroll
+    for (int j = 0; j < DR_NS; ++j) lo[j] = slot_lo(j);
+    // DR_D register sets: the workgroup's chunk i lives in set i % DR_D from DR_D chunk periods before it
+    // is split into buffer i & 1.  roll(Q, c): the set of the chunk due in buffer Q is split there, each
+    // slot reloaded with chunk c's (DR_D chunks later) as soon as it is consumed, so DR_D whole chunks
+    // (25.6 KB each) stay in flight.  Unconditional: past the end zeros go to the idle buffer
+    f32x4 v[DR_D][DR_NS];
+    auto roll = [&](auto Q_, int c) {
+      constexpr int Q = decltype(Q_)::value, S = Q % DR_D;
+      const rsrc_t rd = drsrc(c);
+#pragma unroll
+      for (int j = 0; j < DR_NS; ++j) {
+        split3_store(v[S][j], dsm + Q * DS4_BUF + lo[j], DS4_PL);
+        v[S][j] = ld4(rd, 16 * (lane + 64 * j));
+      }
+    };
+#pragma unroll
+    for (int s = 0; s < DR_D; ++s) {
+      const rsrc_t rd = drsrc(cb + s * cs);
+#pragma unroll
+      for (int j = 0; j < DR_NS; ++j) v[s][j] = ld4(rd, 16 * (lane + 64 * j));
+    }
+    roll(I0{}, cb + DR_D * cs);
+    lds_barrier();
+    // chunk cc (buffer P) is being consumed: chunk cc + cs into buffer P ^ 1
+    for (int cc = cb;;) {
+      roll(I1{}, cc + (1 + DR_D) * cs);
+      lds_barrier();
+      if ((cc += cs) >= nch) break;
+      roll(I0{}, cc + (1 + DR_D) * cs);
+      lds_barrier();
+      if ((cc += cs) >= nch) break;
+    }
+  }
+}
+
 // ==========================================================================================
 // fp32 input gradient dX = dZ W^T   (dZ: M x 400, W: KO x 400 row-major, dX: M x KO, KO <= 16 NT)
 // ==========================================================================================
@@ -1362,13 +1572,22 @@ bool launch_lstmf_wgrad(const float* X, const float* Hs, const float* D, const f
 
 bool lstmf_dgrad_supported(int N, int KO) { return N == FG && KO >= 1 && KO <= 16 * FNT; }
 
-// impl 1 / 3: the exact-fp32 MFMA kernel / the LDS-staged split kernel lstmf_dgrad_s4_kernel; default
-// (0): exact under HFREP_FP32_EXACT, else s4 for KO > 64 and exact otherwise (s4 keeps one wave busy
-// per 32 output columns, so KO = 32 leaves three SIMDs idle; profiles/r03_split)
+// impl 1 / 3 / 4: the exact-fp32 MFMA kernel / the LDS-staged split kernel lstmf_dgrad_s4_kernel / the
+// split with MFMA and staging wave roles lstmf_dgrad_roles_kernel (bitwise equal to impl 3); default (0):
+// exact under HFREP_FP32_EXACT, else the role kernel for KO > 64 and exact otherwise (the split kernels
+// keep one wave busy per 16 / 32 output columns, so KO = 32 leaves most of the matrix pipe idle;
+// profiles/r03_split, profiles/dgrad_roles).  s4 is reached by impl = 3 only: the reference of the tests.
 bool launch_lstmf_dgrad(const float* D, const float* W, float* X, int M, int N, int KO, hipStream_t s, int impl) {
   if (!lstmf_dgrad_supported(N, KO) || M <= 0) return false;
-  const int dv = impl == 1 || impl == 3 ? impl : (fp32_exact() ? 1 : 0);
-  if (dv == 3 || (dv == 0 && KO > 64)) {
+  const int dv = impl == 1 || impl == 3 || impl == 4 ? impl : (fp32_exact() ? 1 : 0);
+  if (dv == 4 || (dv == 0 && KO > 64)) {
+    const int chunks = (M + 15) / 16, cus = device_cu_count();
+    const int grid = chunks < cus ? chunks : cus;
+    allow_lds(reinterpret_cast<const void*>(lstmf_dgrad_roles_kernel));
+    hipLaunchKernelGGL(lstmf_dgrad_roles_kernel, dim3(grid), dim3(512), (size_t)2 * DS4_BUF, s, D, W, X, M, KO);
+    return true;
+  }
+  if (dv == 3) {
     const int chunks = (M + 15) / 16, cus = device_cu_count();
     const int grid = chunks < cus ? chunks : cus;
     auto go = [&](auto k) {

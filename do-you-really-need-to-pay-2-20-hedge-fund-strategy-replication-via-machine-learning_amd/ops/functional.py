@@ -95,7 +95,7 @@ def linear(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, act: int,
 
 
 # fp32 dZ (.., 400) @ W^T with W (K <= 112, 400): the LSTM layers' input gradient, on the native
-# kernels of csrc/lstmf_grad.hip (lstmf_dgrad_s4 split / lstmf_dgrad exact)
+# kernels of csrc/lstmf_grad.hip (lstmf_dgrad_roles split for K > 64 / lstmf_dgrad exact below)
 
 
 def linear_dgrad(dz: torch.Tensor, W: torch.Tensor) -> torch.Tensor:

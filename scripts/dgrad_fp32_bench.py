@@ -1,7 +1,15 @@
-"""fp32 LSTM input gradient dZ W^T: csrc/lstm_f32.hip lstmf_dgrad_kernel vs torch.mm (hipBLASLt).
+"""fp32 LSTM input gradient dX = dZ W^T (csrc/lstmf_grad.hip), per call: the A/B tool of the op's impls.
 
-usage: python scripts/dgrad_fp32_bench.py [M ...]   (GPU only; one JSON line per (M, KO))
+impl 1 = lstmf_dgrad_kernel (exact fp32 MFMA), 3 = lstmf_dgrad_s4_kernel (split, every wave every job),
+4 = lstmf_dgrad_roles_kernel (split, MFMA / staging wave roles; bitwise equal to 3).  Each case (M, KO, impl)
+is timed `--repeats` times (`--iters` calls per repeat between two events) and gives one JSON line with the
+minimum, the range of the repeats and the max |difference| against impl 3.  For a library that predates an
+impl pass `--impls` without it (an unknown impl runs the default kernel); HFREP_NATIVE_LIB picks the library.
+
+usage: python scripts/dgrad_fp32_bench.py [--M 6291456 12582912] [--KO 100] [--impls 1 3 4] [--repeats 3]
+(GPU only)
 """
+import argparse
 import json
 import os
 import sys
@@ -13,41 +21,47 @@ import hfrep  # noqa: E402,F401
 from hfrep.ops import _native  # noqa: E402
 
 
-def timeit(fn, reps=10):
-    fn()
+def timeit(fn, iters):
     torch.cuda.synchronize()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
-    for _ in range(reps):
+    for _ in range(iters):
         fn()
     e.record()
     torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+    return s.elapsed_time(e) / iters
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--M", type=int, nargs="+", default=[6291456, 12582912])
+    ap.add_argument("--KO", type=int, nargs="+", default=[100])
+    ap.add_argument("--impls", type=int, nargs="+", default=[1, 3, 4])
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--label", default=os.environ.get("HFREP_NATIVE_LIB", "default"))
+    a = ap.parse_args()
     ops = _native.native()
     dev = torch.device("cuda")
-    Ms = [int(a) for a in sys.argv[1:]] or [786432, 6291456]
     g = torch.Generator(device=dev).manual_seed(0)
-    for M in Ms:
+    for M in a.M:
         dz = torch.randn(M, 400, device=dev, generator=g)
-        for KO in (100, 32):
+        for KO in a.KO:
             W = torch.randn(KO, 400, device=dev, generator=g) * 0.1
-            fl = 2.0 * M * 400 * KO
-            t_n = timeit(lambda: ops.lstmf_dgrad(dz, W, 1))
-            t_s = timeit(lambda: ops.lstmf_dgrad(dz, W, 2))
-            t_4 = timeit(lambda: ops.lstmf_dgrad(dz, W, 3))
-            t_t = timeit(lambda: torch.mm(dz, W.t()))
-            diff = (ops.lstmf_dgrad(dz, W, 1) - torch.mm(dz, W.t())).abs().max().item()
-            diff_s = (ops.lstmf_dgrad(dz, W, 2) - ops.lstmf_dgrad(dz, W, 1)).abs().max().item()
-            diff_4 = (ops.lstmf_dgrad(dz, W, 3) - ops.lstmf_dgrad(dz, W, 1)).abs().max().item()
-            print(json.dumps({"op": "lstmf_dgrad", "M": M, "KO": KO, "native_ms": round(t_n, 3),
-                              "split_ms": round(t_s, 3), "split_lds_ms": round(t_4, 3), "hipblaslt_ms": round(t_t, 3),
-                              "native_tf": round(fl / t_n / 1e9, 1), "split_tf": round(fl / t_s / 1e9, 1),
-                              "hipblaslt_tf": round(fl / t_t / 1e9, 1), "split_GBs": round(M * 400 * 4 / t_s / 1e6, 0),
-                              "maxdiff": diff, "split_vs_exact_maxdiff": diff_s, "split_lds_vs_exact_maxdiff": diff_4}),
-                  flush=True)
+            ref = ops.lstmf_dgrad(dz, W, 3)
+            for impl in a.impls:
+                x = ops.lstmf_dgrad(dz, W, impl)  # (also the warm-up call)
+                diff = (x - ref).abs().max().item()
+                del x
+                ts = [timeit(lambda: ops.lstmf_dgrad(dz, W, impl), a.iters) for _ in range(a.repeats)]
+                t = min(ts)
+                print(json.dumps({"op": "lstmf_dgrad", "lib": a.label, "M": M, "KO": KO, "impl": impl,
+                                  "min_ms": round(t, 4), "range_ms": [round(min(ts), 4), round(max(ts), 4)],
+                                  "repeats_ms": [round(v, 4) for v in ts], "iters": a.iters,
+                                  "tflops": round(2.0 * M * 400 * KO / t / 1e9, 1),
+                                  "GBs": round(M * (400 + KO) * 4 / t / 1e6, 0),
+                                  "maxdiff_vs_impl3": diff}), flush=True)
+            del ref
         del dz
         torch.cuda.empty_cache()
 
