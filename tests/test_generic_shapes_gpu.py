@@ -14,7 +14,8 @@ import torch
 import test_kernels_gpu as TK
 from _generic_shapes import ACTS, H, LSTM_SHAPES, lstm_inputs
 from hfrep.ops import reference as R
-from test_kernels_gpu import BF16_BLOCK, BF16_GLOBAL, _block_errors, _close, _ops
+from _blocks import BF16_GLOBAL, VANISHED, assert_blocks_close, cpu_twin, wasserstein_half_scales
+from test_kernels_gpu import _close, _ops
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -187,6 +188,9 @@ def test_lstm_wgrad_fused_generic_width(cuda, B, T, K, tangent):
 # ---------------------------------------------------------------------------------------------------
 # 3. end to end at generic feature counts
 # ---------------------------------------------------------------------------------------------------
+HEAD = VANISHED["lstm", "wgan_gp"]  # the critic's head bias: zero in a whole update (tests/_blocks.py)
+
+
 def _trainers(cuda, dtype, F, T=6, B=40):
     from hfrep.train.gan_trainer import GANConfig, GANTrainer
 
@@ -213,18 +217,13 @@ def test_trainer_gradients_generic_features_fp32(cuda, F):
         fg = tg.generator.predict(noise.to(cuda))
         fc = tc.generator.predict(noise.double())
         _close(fg, fc, torch.float32)
+        scales = wasserstein_half_scales(tc, real.double(), HEAD)
         tg.critic_gp_grads(real.to(cuda), fg, alpha.to(cuda))
         tc.critic_gp_grads(real.double(), fg.double().cpu(), alpha.double())
-        gg, gc = tg.critic.flat.grad.cpu().double(), tc.critic.flat.grad
-        rel = (gg - gc).norm() / gc.norm()
-        print(f"F = {F} critic fp32 grad rel err {rel:.3e}")
-        assert rel < 2e-4, f"critic grad rel err {rel:.2e}"
+        assert_blocks_close(tg.critic, tc.critic, "float32", HEAD, scales, f"F = {F} critic fp32", flat_tol=2e-4)
         lg = tg.generator_grads(noise.to(cuda))
         lc = tc.generator_grads(noise.double())
-        gg, gc = tg.generator.flat.grad.cpu().double(), tc.generator.flat.grad
-        rel = (gg - gc).norm() / max(gc.norm(), 1e-30)
-        print(f"F = {F} generator fp32 grad rel err {rel:.3e}")
-        assert rel < 2e-4, f"generator grad rel err {rel:.2e}"
+        assert_blocks_close(tg.generator, tc.generator, "float32", label=f"F = {F} generator fp32", flat_tol=2e-4)
         assert abs(lg.item() - lc.item()) < 1e-4 * max(1, abs(lc.item()))
 
 
@@ -235,21 +234,23 @@ def test_trainer_gradients_generic_features_bf16(cuda, F):
     T, B = 6, 40
     tg, tc = _trainers(cuda, "bfloat16", F)
     g = torch.Generator().manual_seed(12)
-    real = torch.rand(B, T, F, generator=g)
-    noise = torch.randn(B, T, F, generator=g)
+    real = torch.rand(B, T, F, generator=g).to(BF)
+    noise = torch.randn(B, T, F, generator=g).to(BF)
     alpha = torch.rand(B, generator=g)
+    tb = cpu_twin(tg, "bfloat16")  # the CPU bf16 engine: a block's bound is max(5e-2, 2 e_cpu), tests/_blocks.py
     with torch.no_grad():
-        fg = tg.generator.predict(noise.to(cuda, BF))
-        tg.critic_gp_grads(real.to(cuda, BF), fg, alpha.to(cuda))
-        tc.critic_gp_grads(real.to(BF).double(), fg.double().cpu(), alpha.double())
-        rel, worst, name = _block_errors(tg.critic, tc.critic)
-        print(f"F = {F} critic bf16 rel {rel:.3e} worst block {worst:.3e} ({name})")
-        assert rel < BF16_GLOBAL and worst < BF16_BLOCK, (rel, worst, name)
-        tg.generator_grads(noise.to(cuda, BF))
-        tc.generator_grads(noise.to(BF).double())
-        rel, worst, name = _block_errors(tg.generator, tc.generator)
-        print(f"F = {F} generator bf16 rel {rel:.3e} worst block {worst:.3e} ({name})")
-        assert rel < BF16_GLOBAL and worst < BF16_BLOCK, (rel, worst, name)
+        fg = tg.generator.predict(noise.to(cuda))
+        scales = wasserstein_half_scales(tc, real.double(), HEAD)
+        tg.critic_gp_grads(real.to(cuda), fg, alpha.to(cuda))
+        tc.critic_gp_grads(real.double(), fg.double().cpu(), alpha.double())
+        tb.critic_gp_grads(real, fg.cpu(), alpha)
+        assert_blocks_close(tg.critic, tc.critic, "bfloat16", HEAD, scales, f"F = {F} critic bf16", flat_tol=BF16_GLOBAL,
+                            model_cpu=tb.critic)
+        tg.generator_grads(noise.to(cuda))
+        tc.generator_grads(noise.double())
+        tb.generator_grads(noise)
+        assert_blocks_close(tg.generator, tc.generator, "bfloat16", label=f"F = {F} generator bf16",
+                            flat_tol=BF16_GLOBAL, model_cpu=tb.generator)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from _blocks import BF16_GLOBAL, VANISHED, assert_blocks_close, block_errors, cpu_twin, wasserstein_half_scales
 from hfrep.ops import reference as R
 
 pytestmark = pytest.mark.gpu
@@ -303,7 +304,8 @@ def test_optimizers_match_cpu(cuda):
                                            (("lstm", "wgan_gp"), 168, 36, True)])
 def test_trainer_gradients_gpu_vs_cpu(cuda, key, T, F, lrelu):
     """The full explicit critic/generator gradient programs on GPU (native fp32 kernels) vs CPU fp64,
-    incl. the production generator shape (T = 168, F = 36, LeakyReLU after the first LSTM)."""
+    incl. the production generator shape (T = 168, F = 36, LeakyReLU after the first LSTM): the
+    flat gradient and every parameter block and LSTM gate on its own (tests/_blocks.py)."""
     from hfrep.train.gan_trainer import GANConfig, GANTrainer
 
     B = 48
@@ -325,16 +327,14 @@ def test_trainer_gradients_gpu_vs_cpu(cuda, key, T, F, lrelu):
             fg = tg.generator.predict(noise.to(cuda))
             fc = tc.generator.predict(noise.double())
             _close(fg, fc, torch.float32)
+            scales = wasserstein_half_scales(tc, real.double(), VANISHED[key])
             tg.critic_gp_grads(real.to(cuda), fg, alpha.to(cuda))
             tc.critic_gp_grads(real.double(), fg.double().cpu(), alpha.double())
-            gg, gc = tg.critic.flat.grad.cpu().double(), tc.critic.flat.grad
-            rel = (gg - gc).norm() / gc.norm()
-            assert rel < 2e-4, f"critic grad rel err {rel:.2e}"
+            assert_blocks_close(tg.critic, tc.critic, "float32", VANISHED[key], scales, f"{key} T {T} critic",
+                                flat_tol=2e-4)
         lg = tg.generator_grads(noise.to(cuda))
         lc = tc.generator_grads(noise.double())
-        gg, gc = tg.generator.flat.grad.cpu().double(), tc.generator.flat.grad
-        rel = (gg - gc).norm() / max(gc.norm(), 1e-30)
-        assert rel < 2e-4, f"generator grad rel err {rel:.2e}"
+        assert_blocks_close(tg.generator, tc.generator, "float32", label=f"{key} T {T} generator", flat_tol=2e-4)
         assert abs(lg.item() - lc.item()) < 1e-4 * max(1, abs(lc.item()))
 
 
@@ -385,68 +385,83 @@ def test_lstm2_fused_layer(cuda, act, B, T, K):
         _close(dXd3, rzd @ Wd.t(), torch.bfloat16, scale=(rzd.abs() @ Wd.abs().t()).max().item())
 
 
-def _block_errors(model_g, model_c):
-    """(global relative L2 error, worst per-parameter-block relative L2 error, block name) of the
-    flat gradients of two copies of one model (every Keras weight is its own block, so an error in
-    one layer cannot be averaged away by the others)."""
-    a_all, b_all = model_g.flat.grad.cpu().double(), model_c.flat.grad.double().cpu()
-    # a block whose exact gradient vanishes (the critic head bias under the Wasserstein terms:
-    # sum of -1/B over real + 1/B over fake = 0) is measured against 1e-3 of the whole gradient
-    floor = 1e-3 * b_all.norm().item()
-    worst, wname = 0.0, ""
-    for (name, _), (_, _) in zip(model_g.named_weights(), model_c.named_weights()):
-        lay = [l for l in model_g.layers for s_ in l.specs if s_.keras == name][0]
-        spec = [s_ for s_ in lay.specs if s_.keras == name][0]
-        n = int(np.prod(spec.shape))
-        a, b = a_all[spec.offset:spec.offset + n], b_all[spec.offset:spec.offset + n]
-        rel = ((a - b).norm() / max(b.norm().item(), floor, 1e-30)).item()
-        if rel > worst:
-            worst, wname = rel, name
-    return ((a_all - b_all).norm() / max(b_all.norm().item(), 1e-30)).item(), worst, wname
-
-
-# bf16 bounds.  Measured on MI355X (r02, profiles/r02_tests/bf16_errors.txt): global 2.7e-3 .. 5.9e-3,
-# worst block 4.0e-3 .. 2.3e-2 (the generator's first LSTM kernel at T = 168).  The compute is bf16
-# MFMA with bf16 activations / tapes against an fp64 reference of the same inputs, so ~1e-2 is the
-# bf16 noise floor; a stale or wrong row tile moves these by O(0.1 .. 1)
-BF16_GLOBAL, BF16_BLOCK = 1.5e-2, 5e-2
-
-
 @pytest.mark.parametrize("key,T,F,B,lrelu", [(("lstm", "wgan_gp"), 24, 32, 64, False), (("lstm", "wgan"), 24, 32, 64, False),
                                              (("lstm", "wgan_gp"), 24, 32, 256 * 32 + 70, False),
                                              (("lstm", "wgan_gp"), 168, 36, 40, True),
                                              (("lstm_ln", "wgan_gp"), 24, 32, 64, False)])
 def test_trainer_gradients_bf16_fused(cuda, key, T, F, B, lrelu):
     """bf16 training step (fused LSTM kernels) vs the fp64 CPU engine: norm-relative error of the
-    whole gradient and of every parameter block.  Cases: the bench shape at small B, a multi-pass
-    batch (more 32-row tiles than CUs + a partial tile), and the production generator shape
-    (T = 168, F = 36, LeakyReLU after the first LSTM)."""
+    whole gradient and of every parameter block and LSTM gate (tests/_blocks.py; the bounds and their
+    measurements: docs/TEST_TOLERANCES.md).  Cases: the bench shape at small B, a multi-pass batch (more
+    32-row tiles than CUs + a partial tile), and the production generator shape (T = 168, F = 36,
+    LeakyReLU after the first LSTM)."""
     from hfrep.train.gan_trainer import GANConfig, GANTrainer
 
     ds = np.random.RandomState(0).rand(64, T, F).astype(np.float32)
     kw = dict(arch=key[0], loss=key[1], window=T, features=F, batch_size=B, lrelu_after_first=lrelu)
     tg = GANTrainer(GANConfig(dtype="bfloat16", **kw), ds, device=cuda)
-    tc = GANTrainer(GANConfig(dtype="float64", **kw), ds, param_dtype=torch.float64)
-    with torch.no_grad():
-        tc.generator.flat.copy_(tg.generator.flat.double().cpu())
-        tc.critic.flat.copy_(tg.critic.flat.double().cpu())
+    tc = cpu_twin(tg, "float64")
+    # the CPU bf16 engine's own per-block error raises a block's bound to 2 e_cpu (tests/_blocks.py); at the
+    # multi-pass batch and at T = 168 it is too slow, and the plain bound has been measured there
+    tb = cpu_twin(tg, "bfloat16") if B <= 64 and T == 24 else None
     g = torch.Generator().manual_seed(12)
-    real = torch.rand(B, T, F, generator=g)
-    noise = torch.randn(B, T, F, generator=g)
+    real = torch.rand(B, T, F, generator=g).to(torch.bfloat16)
+    noise = torch.randn(B, T, F, generator=g).to(torch.bfloat16)
     alpha = torch.rand(B, generator=g)
+    tag = f"{key} {B}x{T}x{F} bf16"
     with torch.no_grad():
         if key[1] == "wgan_gp":
-            fg = tg.generator.predict(noise.to(cuda, torch.bfloat16))
-            tg.critic_gp_grads(real.to(cuda, torch.bfloat16), fg, alpha.to(cuda))
-            tc.critic_gp_grads(real.to(torch.bfloat16).double(), fg.double().cpu(), alpha.double())
-            rel, worst, name = _block_errors(tg.critic, tc.critic)
-            print(f"critic bf16 rel {rel:.3e} worst block {worst:.3e} ({name})")
-            assert rel < BF16_GLOBAL and worst < BF16_BLOCK, (rel, worst, name)
-        tg.generator_grads(noise.to(cuda, torch.bfloat16))
-        tc.generator_grads(noise.to(torch.bfloat16).double())
-        rel, worst, name = _block_errors(tg.generator, tc.generator)
-        print(f"generator bf16 rel {rel:.3e} worst block {worst:.3e} ({name})")
-        assert rel < BF16_GLOBAL and worst < BF16_BLOCK, (rel, worst, name)
+            fg = tg.generator.predict(noise.to(cuda))
+            if tb is not None:
+                scales = wasserstein_half_scales(tc, real.double(), VANISHED[key])
+            else:  # the large cases: the head bias alone vanishes, and its real-half term is |sum_r -1/B| = 1
+                assert key == ("lstm", "wgan_gp")
+                scales = {VANISHED[key][0]: 1.0}
+            tg.critic_gp_grads(real.to(cuda), fg, alpha.to(cuda))
+            tc.critic_gp_grads(real.double(), fg.double().cpu(), alpha.double())
+            if tb is not None:
+                tb.critic_gp_grads(real, fg.cpu(), alpha)
+            assert_blocks_close(tg.critic, tc.critic, "bfloat16", VANISHED[key], scales, f"{tag} critic",
+                                flat_tol=BF16_GLOBAL, model_cpu=tb.critic if tb else None)
+        tg.generator_grads(noise.to(cuda))
+        tc.generator_grads(noise.double())
+        if tb is not None:
+            tb.generator_grads(noise)
+        assert_blocks_close(tg.generator, tc.generator, "bfloat16", label=f"{tag} generator", flat_tol=BF16_GLOBAL,
+                            model_cpu=tb.generator if tb else None)
+
+
+def test_trainer_gradients_bf16_conv(cuda):
+    """The conv critic model's bf16 training step vs the fp64 CPU engine, block by block (B = 64, T = 24,
+    F = 32).  The critic (im2col + GEMM kernels) is held to the LSTM models' bounds.  The generator's
+    gradient through this critic is where bf16 itself is loosest: the CPU bf16 engine misses the first LSTM
+    kernel by 0.13 and the flat gradient by 4e-2 (docs/TEST_TOLERANCES.md), so its blocks take the
+    max(5e-2, 2 e_cpu) rule and its flat bound is the same rule on the flat error, max(BF16_GLOBAL, 2 e_cpu)."""
+    from hfrep.train.gan_trainer import GANConfig, GANTrainer
+
+    key, T, F, B = ("conv", "wgan_gp"), 24, 32, 64
+    ds = np.random.RandomState(0).rand(64, T, F).astype(np.float32)
+    tg = GANTrainer(GANConfig(arch=key[0], loss=key[1], window=T, features=F, batch_size=B, dtype="bfloat16"), ds,
+                    device=cuda)
+    tc, tb = cpu_twin(tg, "float64"), cpu_twin(tg, "bfloat16")
+    g = torch.Generator().manual_seed(12)
+    real = torch.rand(B, T, F, generator=g).to(torch.bfloat16)
+    noise = torch.randn(B, T, F, generator=g).to(torch.bfloat16)
+    alpha = torch.rand(B, generator=g)
+    with torch.no_grad():
+        fg = tg.generator.predict(noise.to(cuda))
+        scales = wasserstein_half_scales(tc, real.double(), VANISHED[key])
+        tg.critic_gp_grads(real.to(cuda), fg, alpha.to(cuda))
+        tc.critic_gp_grads(real.double(), fg.double().cpu(), alpha.double())
+        tb.critic_gp_grads(real, fg.cpu(), alpha)
+        assert_blocks_close(tg.critic, tc.critic, "bfloat16", VANISHED[key], scales, "conv bf16 critic",
+                            flat_tol=BF16_GLOBAL, model_cpu=tb.critic)
+        tg.generator_grads(noise.to(cuda))
+        tc.generator_grads(noise.double())
+        tb.generator_grads(noise)
+        e_cpu = block_errors(tb.generator, tc.generator)[0]
+        assert_blocks_close(tg.generator, tc.generator, "bfloat16", label="conv bf16 generator",
+                            flat_tol=max(BF16_GLOBAL, 2.0 * e_cpu), model_cpu=tb.generator)
 
 
 @pytest.mark.parametrize("impl", [0, 2])
@@ -974,17 +989,6 @@ def test_gan_eval_device_path(cuda):
         assert abs(a - b) <= 1e-4 * max(abs(b), 1e-3), (name, a, b)
 
 
-def _block_rel(model, a, b):
-    """{keras weight name: relative L2 error} of two flat gradients of ``model``."""
-    out = {}
-    for lay in model.layers:
-        for sp in lay.specs:
-            n = int(np.prod(sp.shape))
-            x, y = a[sp.offset:sp.offset + n], b[sp.offset:sp.offset + n]
-            out[sp.keras] = ((x - y).norm() / max(y.norm().item(), 1e-30)).item()
-    return out
-
-
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
 @pytest.mark.parametrize("B,T,F,lrelu", [(16384, 24, 32, False), (262144, 24, 32, False), (32768, 168, 36, True)])
 def test_bench_scale_gradients_are_slice_averages(cuda, dtype, B, T, F, lrelu):
@@ -1020,14 +1024,17 @@ def test_bench_scale_gradients_are_slice_averages(cuda, dtype, B, T, F, lrelu):
         # run-to-run bitwise at the full batch (the store-data hazard made reruns differ at 2 x 262k rows)
         assert torch.equal(full, grads(tr.critic, tr.critic_gp_grads, real, fake, alpha)), "critic rerun differs"
         avg = sum(grads(tr.critic, tr.critic_gp_grads, sl(real, i), sl(fake, i), sl(alpha, i)) for i in range(S)) / S
-        rel = ((full - avg).norm() / avg.norm()).item()
-        assert torch.isfinite(full).all() and rel < tol, (f"critic: full-batch vs slice-average rel {rel:.2e}",
-                                                          _block_rel(tr.critic, full, avg))
+        # every block on its own too; the head bias vanishes (sum of -1/B over real and +1/B over fake) and
+        # is measured against its real-half term, |sum_r -1/B| = 1
+        assert torch.isfinite(full).all()
+        head = VANISHED["lstm", "wgan_gp"]
+        assert_blocks_close(tr.critic, tr.critic, dtype, head, {head[0]: 1.0}, f"critic {dtype} B {B} T {T} vs slices",
+                            flat_tol=tol, got=full, ref=avg)
         full = grads(tr.generator, tr.generator_grads, noise)
         avg = sum(grads(tr.generator, tr.generator_grads, sl(noise, i)) for i in range(S)) / S
-        rel = ((full - avg).norm() / avg.norm()).item()
-        assert torch.isfinite(full).all() and rel < tol, (f"generator: full-batch vs slice-average rel {rel:.2e}",
-                                                          _block_rel(tr.generator, full, avg))
+        assert torch.isfinite(full).all()
+        assert_blocks_close(tr.generator, tr.generator, dtype, label=f"generator {dtype} B {B} T {T} vs slices",
+                            flat_tol=tol, got=full, ref=avg)
 
 
 @pytest.mark.parametrize("M,K,N,act", [(6291456 + 5, 100, 32, 0), (1000, 36, 36, 1), (333, 64, 112, 2),

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from _blocks import assert_blocks_close, cpu_twin
+
 pytestmark = pytest.mark.gpu
 
 TOL = {"float32": 2e-4, "bfloat16": 3e-2}
@@ -75,12 +77,14 @@ def test_mlp_wgan_fused_grads(cuda, dtype, B, T, F):
     critic, fused kernels vs the fp64 engine (efwd / gan_loss / ebwd; same weights, same batch).  Shapes:
     whole tiles, a partial last tile (888 rows), the F = 36 tail tile, and 144 000 rows (every wave walks
     several tiles: the per-lane partial sums accumulate across the persistent loop).  Each of the ten
-    critic gradient views and each generator gradient view is also checked non-zero on its own, so a missed
-    slab segment or operand cannot hide in the flat norm (the per-view errors are printed)."""
+    critic gradient views and each generator gradient view is held to the per-block bound on its own
+    (tests/_blocks.py: 2e-4 fp32; bf16 max(5e-2, 2 e_cpu) with the CPU bf16 engine's error where B <= 64), so
+    a missed slab segment or operand cannot hide in the flat norm.  No block vanishes: one label per pass."""
     from hfrep.ops import functional as Fn
 
     tg, tc = _pair(cuda, dtype, B, T, F)
     fz, dt = tg._fused, tg.dtype
+    tb = cpu_twin(tg, "bfloat16") if dtype == "bfloat16" and B <= 64 else None
     real, noise = _inputs(B, T, F)
     lt = LTOL[dtype]
     ref_views = [tc.critic.gview(l, s.name) for l in tc.critic.layers for s in l.specs]
@@ -94,13 +98,18 @@ def test_mlp_wgan_fused_grads(cuda, dtype, B, T, F):
             s, tape = tc.critic.efwd(x.double().cpu(), save=True)
             out, ds = Fn.gan_loss(s, s.numel(), label, label, 0)
             tc.critic.ebwd(tape, ds)
+            if tb is not None:
+                tb.critic.zero_grad()
+                sb, tape_b = tb.critic.efwd(x.cpu(), save=True)
+                tb.critic.ebwd(tape_b, Fn.gan_loss(sb, sb.numel(), label, label, 0)[1])
             rel = _rel(tg.critic.flat.grad, tc.critic.flat.grad)
             print(f"[{dtype} {B}x{T}x{F} label {label:+.0f}] critic flat rel {rel:.3e} loss {lg.item():.6f} "
                   f"ref {out[0].item():.6f}")
             for name, got, ref in zip(CRITIC_NAMES, fz.cg, ref_views):
                 r = _rel(got, ref)
                 print(f"    {name}: rel {r:.3e} |ref| {ref.norm().item():.3e}")
-            assert rel < TOL[dtype], f"critic grad rel err {rel:.2e} (label {label})"
+            assert_blocks_close(tg.critic, tc.critic, dtype, label=f"mlp wgan {dtype} {B}x{T}x{F} critic label {label:+.0f}",
+                                flat_tol=TOL[dtype], model_cpu=tb.critic if tb else None)
             for name, got in zip(CRITIC_NAMES, fz.cg):
                 assert got.abs().sum().item() > 0, f"critic gradient {name} is all zero (label {label})"
             assert abs(lg.item() - out[0].item()) <= lt * max(1.0, abs(out[0].item())), (lg.item(), out[0].item())
@@ -108,9 +117,13 @@ def test_mlp_wgan_fused_grads(cuda, dtype, B, T, F):
         tc.generator.zero_grad()
         lg = fz._generator_grads(noise.to(cuda, dt), fake)
         lc = tc.generator_grads(noise.double())
+        if tb is not None:
+            tb.generator.zero_grad()
+            tb.generator_grads(noise.to(dt))
         rel = _rel(tg.generator.flat.grad, tc.generator.flat.grad)
         print(f"[{dtype} {B}x{T}x{F}] generator flat rel {rel:.3e} loss {lg.item():.6f} ref {lc.item():.6f}")
-        assert rel < TOL[dtype], f"generator grad rel err {rel:.2e}"
+        assert_blocks_close(tg.generator, tc.generator, dtype, label=f"mlp wgan {dtype} {B}x{T}x{F} generator",
+                            flat_tol=TOL[dtype], model_cpu=tb.generator if tb else None)
         for i, g in enumerate(fz.gg):
             assert g.abs().sum().item() > 0, f"generator gradient view {i} is all zero"
         assert abs(lg.item() - lc.item()) <= lt * max(1.0, abs(lc.item())), (lg.item(), lc.item())
