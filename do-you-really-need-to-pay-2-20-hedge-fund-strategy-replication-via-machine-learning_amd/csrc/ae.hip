@@ -154,7 +154,7 @@ ae_fit_kernel(const AeFitJob* __restrict__ jobs, int batch, float lr, float b1, 
       const float mt = b1 * (1.f - 0.5f * powf(0.96f, 0.004f * local_step));
       const float mt1 = b1 * (1.f - 0.5f * powf(0.96f, 0.004f * next_step));
       const float sched_new = mc * mt, sched_next = sched_new * mt1;
-      const float vden = 1.f - powf(b2, local_step);
+      const float vden = -expm1f(local_step * logf(b2));  // 1 - b2^t without the cancellation (optim.hip)
       for (int e = tid; e < 2 * nW; e += AE_THREADS) {
         const bool enc = e < nW;
         const int i = enc ? e : e - nW;

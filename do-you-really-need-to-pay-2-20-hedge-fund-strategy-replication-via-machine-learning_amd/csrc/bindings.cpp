@@ -764,6 +764,7 @@ Tensor interpolate(Tensor real, Tensor fake, Tensor alpha) {
 void philox_fill_(Tensor out, int64_t seed, Tensor ctr, int64_t dist) {
   CHECK_GPU(out);
   TORCH_CHECK(ctr.is_cuda() && ctr.scalar_type() == at::kLong && ctr.numel() == 1, "ctr must be a 1-element int64 GPU tensor");
+  TORCH_CHECK(dist == 0 || dist == 1, "philox_fill_: dist must be 0 (uniform) or 1 (normal), got ", dist);
   GUARD(out);
   hfrep::launch_philox_fill(dt_of(out), out.data_ptr(), out.numel(), (uint64_t)seed, ctr.data_ptr<int64_t>(), (int)dist,
                             cur_stream(out));
@@ -860,6 +861,10 @@ std::tuple<Tensor, Tensor> ae_fit(at::TensorList Xt, at::TensorList Xv, at::Tens
 }
 
 // ------------------------------------------------------------------------------------ optimizers
+// the device-resident scalars (iterations, Nadam momentum cache): one element, on the parameters' device
+#define CHECK_COUNTER(t, like, what) \
+  TORCH_CHECK((t).numel() == 1 && (t).device() == (like).device(), what " must have one element on the parameters' device")
+
 void rmsprop_(Tensor p, Tensor g, Tensor ms, double lr, double rho, double eps, double clip, double gscale) {
   CHECK_F32(p); CHECK_F32(g); CHECK_F32(ms);
   TORCH_CHECK(p.numel() == g.numel() && p.numel() == ms.numel(), "rmsprop_: size mismatch");
@@ -872,6 +877,7 @@ void adam_(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step, double lr, doubl
            double clip, double gscale) {
   CHECK_F32(p); CHECK_F32(g); CHECK_F32(m); CHECK_F32(v); CHECK_F32(step);
   TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "adam_: size mismatch");
+  CHECK_COUNTER(step, p, "adam_: step");
   GUARD(p);
   hfrep::launch_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), p.numel(),
                      step.data_ptr<float>(), (float)lr, (float)b1, (float)b2, (float)eps, (float)clip, (float)gscale,
@@ -881,6 +887,9 @@ void adam_(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step, double lr, doubl
 void nadam_(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step, Tensor m_cache, double lr, double b1, double b2,
             double eps, double gscale) {
   CHECK_F32(p); CHECK_F32(g); CHECK_F32(m); CHECK_F32(v); CHECK_F32(step); CHECK_F32(m_cache);
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "nadam_: size mismatch");
+  CHECK_COUNTER(step, p, "nadam_: step");
+  CHECK_COUNTER(m_cache, p, "nadam_: m_cache");
   GUARD(p);
   hfrep::launch_nadam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), p.numel(),
                       step.data_ptr<float>(), m_cache.data_ptr<float>(), (float)lr, (float)b1, (float)b2, (float)eps,
@@ -889,9 +898,14 @@ void nadam_(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step, Tensor m_cache,
 
 void step_advance_(Tensor step, optional<Tensor> m_cache, double b1) {
   CHECK_F32(step);
+  CHECK_COUNTER(step, step, "step_advance_: step");
   GUARD(step);
   float* mc = nullptr;
-  if (m_cache.has_value()) { CHECK_F32(*m_cache); mc = m_cache->data_ptr<float>(); }
+  if (m_cache.has_value()) {
+    CHECK_F32(*m_cache);
+    CHECK_COUNTER(*m_cache, step, "step_advance_: m_cache");
+    mc = m_cache->data_ptr<float>();
+  }
   hfrep::launch_step_advance(step.data_ptr<float>(), mc, (float)b1, cur_stream(step));
 }
 

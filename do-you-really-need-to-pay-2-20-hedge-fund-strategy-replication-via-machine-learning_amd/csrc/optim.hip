@@ -17,6 +17,11 @@
 
 namespace hfrep {
 
+// 1 - b^t for the second-moment bias correction.  1.f - powf(b, t) cancels: at b = 0.999 the power
+// rounds to within 3e-8 of a value only 1e-3 t below one, a relative 3e-5 / t on the difference (and
+// half that on every step of the first iterations).  -expm1(t log b) keeps it to a few ulp.
+__device__ __forceinline__ float one_minus_pow(float b, float t) { return -expm1f(t * logf(b)); }
+
 // grid-stride, float4-vectorised when aligned
 __global__ void __launch_bounds__(256) rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ ms, int64_t n, float lr, float rho,
@@ -59,7 +64,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
                                                    const float* __restrict__ step_ctr, float lr, float b1,
                                                    float b2, float eps, float clip, float gscale) {
   const float t = step_ctr[0] + 1.0f;
-  const float lr_t = lr * sqrtf(1.f - powf(b2, t)) / (1.f - powf(b1, t));
+  const float lr_t = lr * sqrtf(one_minus_pow(b2, t)) / (1.f - powf(b1, t));
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float gk = g[i] * gscale;
@@ -86,7 +91,7 @@ __global__ void __launch_bounds__(256) nadam_kernel(float* __restrict__ p, const
   const float mt1 = b1 * (1.f - 0.5f * powf(0.96f, 0.004f * next_step));
   const float sched_new = m_cache[0] * mt;
   const float sched_next = sched_new * mt1;
-  const float vden = 1.f - powf(b2, local_step);
+  const float vden = one_minus_pow(b2, local_step);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float gk = g[i] * gscale;

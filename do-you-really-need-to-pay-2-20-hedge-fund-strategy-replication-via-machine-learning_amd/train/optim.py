@@ -24,7 +24,9 @@ class KerasOptimizer:
         self.lr, self.rho, self.b1, self.b2, self.eps = learning_rate, rho, beta_1, beta_2, epsilon
         self.device = torch.device(device)
         self.iterations = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.m_cache = torch.ones(1, dtype=torch.float32, device=self.device)  # Nadam momentum cache
+        # Nadam momentum cache (running product of the schedules); fp32 like Keras' and the kernels', widened
+        # to fp64 by the first update of an fp64 buffer (the CPU fp64 engines are references)
+        self.m_cache = torch.ones(1, dtype=torch.float32, device=self.device)
         self.slots: dict[int, tuple] = {}
 
     @classmethod
@@ -90,6 +92,8 @@ class KerasOptimizer:
                 if clip > 0:
                     ops.clip_(flat, clip)
             return
+        if flat.dtype == torch.float64 and self.m_cache.dtype != torch.float64:
+            self.m_cache = self.m_cache.double()
         g = grad * gscale if gscale != 1.0 else grad
         if self.kind == "rmsprop":
             (ms,) = slots

@@ -75,7 +75,7 @@ def mark(name: str) -> None:
 
 def profile_steps(step_fn, steps: int, out_path: str, row_limit: int = 30) -> str:
     """Run ``step_fn()`` ``steps`` times under torch.profiler; write ``out_path`` (Chrome trace JSON)
-    and ``out_path + '.txt'`` (kernel table sorted by device time).  Returns the table."""
+    and ``out_path + '.txt'`` (kernel table sorted by device time, by CPU time where the steps used no device).  Returns the table."""
     import torch
     from torch.profiler import ProfilerActivity, profile
 
@@ -93,7 +93,10 @@ def profile_steps(step_fn, steps: int, out_path: str, row_limit: int = 30) -> st
         enable(prev)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     prof.export_chrome_trace(out_path)
-    table = prof.key_averages().table(sort_by="cuda_time_total" if gpu else "cpu_time_total", row_limit=row_limit)
+    avgs = prof.key_averages()
+    # steps that ran on the CPU device leave no device time to sort by, even on a machine with a GPU
+    on_device = gpu and any(getattr(e, "device_time_total", 0) or getattr(e, "cuda_time_total", 0) for e in avgs)
+    table = avgs.table(sort_by="cuda_time_total" if on_device else "cpu_time_total", row_limit=row_limit)
     with open(out_path + ".txt", "w") as fh:
         fh.write(table)
     return table
