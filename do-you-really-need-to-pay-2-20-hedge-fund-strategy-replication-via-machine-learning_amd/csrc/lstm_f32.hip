@@ -28,6 +28,12 @@
 //
 // TAN = true is the tangent forward at a saved primal point (ops/reference.py lstm_seq_tfwd with
 // dzx = xd W folded in): zdot_t = xd_t W + hdot_{t-1} U, primal gates / cells read from the tape.
+//
+// The four reverse kernels (lstmf_bwdp / lstmf_bwds: BPTT exact / split; lstmf_tbwdp / lstmf_tbwd1: tangent
+// reverse with two streams / one) take the dZ store share, the exact MFMA role, the BPTT cell adjoint, the
+// tangent step loads, the HEAD row factors and the padded-unit mask from one definition each ("stages the
+// reverse kernels share", above the kernels); the tangent cell adjoint is a helper in lstmf_tbwdp and
+// written out in lstmf_tbwd1, whose bits it would change.
 #include "lstmf_dev.h"
 
 #include <atomic>
@@ -396,37 +402,199 @@ __device__ __forceinline__ void bwdf_tape_load_u(f32x4& tg, float& tcp, float& t
   if constexpr (HEAD) tdh = hdm * ld1(rhw, tok ? hvo : kOOB, sd);
   else tdh = ld1(rdh, tok ? vp : kOOB, sd);
 }
+// ------------------------------------------------------------------------------------------
+// stages the reverse kernels share (lstmf_bwdp / lstmf_tbwdp / lstmf_tbwd1 / lstmf_bwds_kernel): one
+// definition of the dZ store mapping, the exact MFMA role, the BPTT and the tangent cell adjoint, the tangent
+// step loads, the HEAD row factors and the padded-unit mask.  Where a kernel keeps a written-out form, a
+// comment at that site names the measurement (profiles/lstmf_rev_shared/README.md)
+// ------------------------------------------------------------------------------------------
+using I0 = std::integral_constant<int, 0>;
+using I1 = std::integral_constant<int, 1>;
+// wave 3's unit tiles 4..6 are the padding units 100..111: their cells read nothing, carry zeros and write
+// to the trash row
+__device__ __forceinline__ bool unit_ok(int w, int n) { return !(w == 3 && n >= 4); }
+
 // the dz tile (32 rows x [q][u'], u' < 100) -> dZ[:, t, :] (row-major, 4H per row) in 16-byte chunks:
-// threads 0..199 own chunk (tid % 100) of rows 2 k + tid / 100 (k < 16); the row step lives in the
-// uniform soffset, so a thread holds one LDS and one global base (rows past B: voffset out of range)
-struct BwdfStore {
+// threads 0..199 (of a role) own chunk (tid % 100) of rows 2 k + tid / 100 (k < 16); the row step lives in
+// the uniform offset, so a thread holds one LDS and one global base (rows past B: voffset out of range)
+struct RevStore {
   int lo, go, rr;
-  __device__ __forceinline__ void set(int tid, int Tn) {
+  __device__ __forceinline__ RevStore(int tid, int Tn) {
     rr = tid / 100;
     const int ch = tid - 100 * rr, qq = ch / 25, c = ch - 25 * qq;
     lo = (rr & 1) * BZ_LR + qq * BZ_KQ + 4 * c;
     go = tid < 200 ? (rr * Tn * FG + qq * FH + 4 * c) * 4 : kOOB;
   }
-  __device__ __forceinline__ void store(const float* zt, rsrc_t rz, int Tn, int t, int nr) const {
+  // rows of half M of `tile` (holding dz at step ts) -> dZ[:, ts, :]; a half's rows are stable for exactly
+  // the half-phase after the one that completed them.  SB: one schedule region per pair of rows (where the
+  // stores ride on an MFMA role, ahead of its MFMAs)
+  template <int M, bool SB>
+  __device__ __forceinline__ void half(const float* tile, rsrc_t rz, int Tn, int ts, int nr) const {
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(zt + lo + 2 * k * BZ_LR);
-      st16(v, rz, 2 * k + rr < nr, go, (2 * k * Tn + t) * FG * 4);
+    for (int k = 8 * M; k < 8 * M + 8; ++k) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(tile + lo + 2 * k * BZ_LR);
+      st16(v, rz, 2 * k + rr < nr, go, (2 * k * Tn + ts) * FG * 4);
+      if constexpr (SB) {
+        if (k & 1) __builtin_amdgcn_sched_barrier(0);
+      }
     }
   }
 };
 
-// 16-row variant for the tangent reverse: threads 0..199 own chunk tid % 100 of rows 2 k + tid / 100
-__device__ __forceinline__ void bwdf_store16(const float* zt, rsrc_t rz, int Tn, int t, int nr, int tid) {
-  const int rr = tid / 100, ch = tid - 100 * rr, qq = ch / 25, c = ch - 25 * qq;
-  const int lo = (rr & 1) * BZ_LR + qq * BZ_KQ + 4 * c;
-  const int go = tid < 200 ? (rr * Tn * FG + qq * FH + 4 * c) * 4 : kOOB;
+// ---- the exact MFMA role (waves 0..3 of the role-split kernels): tile U^T on v_mfma_f32_16x16x4_f32 ----
+// U^T fragments of wave w's output column tiles 2 w, 2 w + 1 (16 units each; arch VGPRs: at two waves per
+// SIMD the role fits in 256 with U^T taking 200)
+__device__ __forceinline__ void rev_ut_load(float (&ut)[2][FH], const float* __restrict__ U, int w, int c16, int g) {
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(zt + lo + 2 * k * BZ_LR);
-    st16(v, rz, 2 * k + rr < nr, go, (2 * k * Tn + t) * FG * 4);
+  for (int e = 0; e < 2; ++e) {
+    const int j = 16 * (2 * w + e) + c16;
+    const bool ok = j < FH;
+#pragma unroll
+    for (int k = 0; k < FH; ++k) {
+      const float v = U[(ok ? j : 0) * FG + g * FH + k];
+      ut[e][k] = ok ? v : 0.f;
+    }
   }
 }
+// rows 16 M .. 16 M + 15 of tile U^T (tile: a dz-style tile, [q][u'] per row) -> the same rows of the
+// dh-style tile `out`; a schedule barrier after every SB b128 fragment reads
+template <int M, int SB>
+__device__ __forceinline__ void rev_half_a(const float* tile, float* out, const float (&ut)[2][FH], int w, int c16, int g) {
+  f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  const float* ar = tile + (16 * M + c16) * BZ_LR + g * BZ_KQ;
+#pragma unroll
+  for (int jj = 0; jj < FH / 4; ++jj) {
+    const f32x4 a4 = *reinterpret_cast<const f32x4*>(ar + 4 * jj);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      acc[0] = mma4(a4[s], ut[0][4 * jj + s], acc[0]);
+      acc[1] = mma4(a4[s], ut[1][4 * jj + s], acc[1]);
+    }
+    if (jj % SB == SB - 1) __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int col = 16 * (2 * w + e) + c16;
+    if (2 * w + e < 7) {  // (wave 3's second tile is past the 112-unit tile: uniform skip)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) out[(16 * M + 4 * g + i) * BH_LR + col] = acc[e][i];
+    }
+  }
+}
+
+// ---- cell adjoints ----
+// BPTT cell adjoint of one (row, unit) at step t: gates tg = (i, f, g, o), c = c_t, cp = c_{t-1} (0 at t = 0),
+// dh = the step's dH, hrec = dz_{t+1} U^T.  Updates the carry dc, writes dz_t = z4 to the cell's words of the
+// fp32 dz tile (zrow; a padding cell: the trash row) and returns the total h adjoint dht
+template <int ACT>
+__device__ __forceinline__ float bptt_cell(f32x4& z4, float& dc, const f32x4 tg, float c, float cp, float dh, float hrec,
+                                           bool tok, float* zrow, float* trash) {
+  const float ig = tg[0], fg = tg[1], gg = tg[2], og = tg[3];
+  const float dht = dh + hrec;
+  const float ca = act_f(ACT, c);
+  const float dov = dht * ca;
+  const float dct = dc + dht * og * act_dy(ACT, ca);
+  dc = tok ? dct * fg : 0.f;
+  z4[0] = dct * gg * ig * (1.f - ig);
+  z4[1] = dct * cp * fg * (1.f - fg);
+  z4[2] = dct * ig * act_dy(ACT, gg);
+  z4[3] = dov * og * (1.f - og);
+  float* zd = tok ? zrow : trash;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) zd[k * BZ_KQ] = z4[k];
+  return dht;
+}
+
+// tangent-reverse cell adjoint of one (row, unit): primal gates tg and their pre-activation tangents tz,
+// c / cd = c_t / cdot_t, cp / cdp = those of t - 1.  The total adjoint of h_t is dh + *hrec (the step's dH and
+// the cell's word of dz_{t+1} U^T); that of hdot_t is dhd + *hdrec with ZD, and dhd itself without (the
+// single-stream kernel reads it whole, hdrec null).  Updates the carries acn / acdn and writes dz_t to the
+// cell's words zt + zo of the dz tile; ZD: the tangent stream's own dzdot_t to zdt + zo as well.  (The sums
+// are formed here, after the activation terms, and the addresses after the products: the statement order of
+// the kernels this came from, which the packed-math pairing and with it the fused roundings follow)
+template <int ACT, bool ZD>
+__device__ __forceinline__ void tan_cell(float& acn, float& acdn, const f32x4 tg, const f32x4 tz, float c, float cd,
+                                         float cp, float cdp, float dh, const float* hrec, float dhd, const float* hdrec,
+                                         bool tok, float* zt, float* zdt, int zo, float* trash) {
+  const float i_ = tg[0], f_ = tg[1], g_ = tg[2], o_ = tg[3];
+  const float zdi = tz[0], zdf = tz[1], zdg = tz[2], zdo = tz[3];
+  const float si = i_ * (1.f - i_), sf = f_ * (1.f - f_), so = o_ * (1.f - o_), sg = act_dy(ACT, g_);
+  const float idot = si * zdi, fdot = sf * zdf, gdot = sg * zdg, odot = so * zdo;
+  const float ca = act_f(ACT, c), d1 = act_dy(ACT, ca), d2 = act_d2y(ACT, ca);
+  const float a_h = dh + *hrec;
+  float a_hd = dhd;
+  if constexpr (ZD) a_hd = dhd + *hdrec;
+  const float a_od = a_hd * ca;
+  const float a_o = a_h * ca + a_hd * d1 * cd;
+  const float a_cd = acdn + a_hd * o_ * d1;
+  const float a_c = acn + a_h * o_ * d1 + a_hd * (odot * d1 + o_ * d2 * cd);
+  const float a_fd = a_cd * cp, a_id = a_cd * g_, a_gd = a_cd * i_;
+  const float a_f = a_c * cp + a_cd * cdp;
+  const float a_i = a_c * g_ + a_cd * gdot;
+  const float a_g = a_c * i_ + a_cd * idot;
+  acn = tok ? a_c * f_ + a_cd * fdot : 0.f;
+  acdn = tok ? a_cd * f_ : 0.f;
+  const float s2i = si * (1.f - 2.f * i_), s2f = sf * (1.f - 2.f * f_), s2o = so * (1.f - 2.f * o_);
+  const float s2g = act_d2y(ACT, g_);
+  float z4[4];
+  z4[0] = a_i * si + a_id * s2i * zdi;
+  z4[1] = a_f * sf + a_fd * s2f * zdf;
+  z4[2] = a_g * sg + a_gd * s2g * zdg;
+  z4[3] = a_o * so + a_od * s2o * zdo;
+  float* zq = tok ? zt + zo : trash;
+  if constexpr (ZD) {
+    const float zd4[4] = {a_id * si, a_fd * sf, a_gd * sg, a_od * so};
+    float* zdq = tok ? zdt + zo : trash;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      zq[k * BZ_KQ] = z4[k];
+      zdq[k * BZ_KQ] = zd4[k];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) zq[k * BZ_KQ] = z4[k];
+  }
+}
+// the tangent reverse's step loads of cell (half m, unit tile n) at step tt: gates, zdot, c_{tt-1}, cdot_{tt-1}
+// and dH (HEAD: the product hdm * w[tt, unit], whose w is returned for a second factor).  The per-lane part of
+// every address is one of tl, tcl, vp, hvo; the cell's slot and the step go into the uniform soffset, so no
+// per-cell offset registers are hoisted (out-of-range lanes: voffset kOOB, which the range check drops
+// whatever the soffset)
+template <bool HEAD>
+__device__ __forceinline__ float tan_step_load(f32x4& tg, f32x4& tz, float& tcp, float& tcdp, float& tdh, rsrc_t rt,
+                                               rsrc_t rtt, rsrc_t rdh, rsrc_t rhw, int tl, int tcl, int vp, int hvo,
+                                               float hdm, int m, int n, int tt, bool tok) {
+  const int tp = tt > 0 ? tt - 1 : 0;
+  const int sg = tt * FT_STEP * 4 + ftape_slot(m, n), sc = tp * FT_STEP * 4 + ftape_slot(m, n);
+  const int sd = tt * FH * 4 + 16 * n;
+  tg = ld4s(rt, tok ? tl : kOOB, sg);
+  tz = ld4s(rtt, tok ? tl : kOOB, sg);
+  tcp = ld1(rt, (tok && tt > 0) ? tcl : kOOB, sc);
+  tcdp = ld1(rtt, (tok && tt > 0) ? tcl : kOOB, sc);
+  float wv = 0.f;
+  if constexpr (HEAD) {
+    wv = ld1(rhw, tok ? hvo : kOOB, sd);
+    tdh = hdm * wv;
+  } else {
+    tdh = ld1(rdh, tok ? vp : kOOB, sd);
+  }
+  return wv;
+}
+// HEAD: dH is the critic head's outer product f (x) w.  The factor of the lane's two rows
+// (row0 + 16 m + 4 g + q; 0 past B, for an absent factor and without HEAD) and the head weight's descriptor
+template <bool HEAD>
+__device__ __forceinline__ void head_rows(float (&v)[2], const float* f, bool have, int row0, int B, int g, int q) {
+  v[0] = v[1] = 0.f;
+  if constexpr (HEAD) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int r = row0 + 16 * m + 4 * g + q;
+      v[m] = (have && r < B) ? f[r] : 0.f;
+    }
+  }
+}
+template <bool HEAD>
+__device__ __forceinline__ rsrc_t head_rsrc(const float* hw, int Tn) { return make_rsrc(hw, HEAD ? Tn * FH * 4 : 0); }
 
 // ------------------------------------------------------------------------------------------
 // BPTT with a role split and a row-half pipeline (8 waves, two per SIMD).
@@ -465,48 +633,15 @@ lstmf_bwdp_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
   if (wv < 4) {
     // ---------------- MFMA role ----------------
     float ut[2][FH];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int j = 16 * (2 * w + e) + c16;
-      const bool ok = j < FH;
-#pragma unroll
-      for (int k = 0; k < FH; ++k) {
-        const float v = U[(ok ? j : 0) * FG + g * FH + k];
-        ut[e][k] = ok ? v : 0.f;  // (arch VGPRs: at two waves per SIMD the role fits in 256)
-      }
-    }
-    // rows of half M of dh_rec = dz[rows M] U^T -> the dh tile
-    auto half_a = [&](auto MA_) {
-      constexpr int M = decltype(MA_)::value;
-      f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      const float* ar = zt + (16 * M + c16) * BZ_LR + g * BZ_KQ;
-#pragma unroll
-      for (int jj = 0; jj < FH / 4; ++jj) {
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(ar + 4 * jj);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          acc[0] = mma4(a4[s], ut[0][4 * jj + s], acc[0]);
-          acc[1] = mma4(a4[s], ut[1][4 * jj + s], acc[1]);
-        }
-        if ((jj & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int col = 16 * (2 * w + e) + c16;
-        if (2 * w + e < 7) {  // (wave 3's second tile is past the 112-unit tile: uniform skip)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) ht[(16 * M + 4 * g + i) * BH_LR + col] = acc[e][i];
-        }
-      }
-    };
+    rev_ut_load(ut, U, w, c16, g);
     for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
       for (int i = tid; i < 32 * BZ_LR; i += 512) zt[i] = 0.f;  // dz_T = 0
       for (int i = tid; i < 32 * BH_LR; i += 512) ht[i] = 0.f;  // dh_rec(T - 1) = 0
       __syncthreads();
       for (int t = Tn - 1; t >= 0; --t) {
-        half_a(std::integral_constant<int, 1>{});  // P1(t): A(1, t)
+        rev_half_a<1, 4>(zt, ht, ut, w, c16, g);  // P1(t): A(1, t)
         lds_barrier();
-        half_a(std::integral_constant<int, 0>{});  // P2(t): A(0, t - 1)
+        rev_half_a<0, 4>(zt, ht, ut, w, c16, g);  // P2(t): A(0, t - 1)
         lds_barrier();
       }
       __syncthreads();
@@ -516,10 +651,7 @@ lstmf_bwdp_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
     const int ct = tid - 256;
     const int ub = FUW * w + j4;
     const int hr = (4 * g + q) * BH_LR + ub, zw = (4 * g + q) * BZ_LR + ub;
-    // dZ store share: threads 0..199 of the role own chunk ct % 100 of rows 2 k + ct / 100 (k < 16)
-    const int srr = ct / 100, sch = ct - 100 * srr, sqq = sch / 25, sc = sch - 25 * sqq;
-    const int slo = (srr & 1) * BZ_LR + sqq * BZ_KQ + 4 * sc;
-    const int sgo = ct < 200 ? (srr * Tn * FG + sqq * FH + 4 * sc) * 4 : kOOB;
+    const RevStore st(ct, Tn);  // threads 0..199 of the role
     const int tl = ftape_lane(w, lane), tcl = ftape_cell(w, lane);
     for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
       const int row0 = rb * 32;
@@ -536,7 +668,7 @@ lstmf_bwdp_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int n = 0; n < FNT; ++n) {
-          const bool tok = !(w == 3 && n >= 4);
+          const bool tok = unit_ok(w, n);
           const int T1 = Tn - 1;
           dc[m][n] = 0.f;
           tc[m][n] = ld1(rt, tok ? tcl + T1 * FT_STEP * 4 + ftape_slot(m, n) : kOOB, 0);  // c_{T-1}
@@ -546,35 +678,15 @@ lstmf_bwdp_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
       for (int i = tid; i < 32 * BZ_LR; i += 512) zt[i] = 0.f;
       for (int i = tid; i < 32 * BH_LR; i += 512) ht[i] = 0.f;
       __syncthreads();
-      // rows of half M of the dz tile (dz at step ts) -> dZ[:, ts, :]
-      auto store_half = [&](auto M_, int ts) {
-        constexpr int M = decltype(M_)::value;
-#pragma unroll
-        for (int k = 8 * M; k < 8 * M + 8; ++k) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(zt + slo + 2 * k * BZ_LR);
-          st16(v, rz, 2 * k + srr < nr, sgo, (2 * k * Tn + ts) * FG * 4);
-        }
-      };
       // cell adjoints of row half M at step t; each cell then issues step t - 1's tape loads
       auto half_b = [&](auto M_, int t) {
         constexpr int m = decltype(M_)::value;
 #pragma unroll
         for (int n = 0; n < FNT; ++n) {
-          const bool tok = !(w == 3 && n >= 4);
-          const float ig = tg[m][n][0], fg = tg[m][n][1], gg = tg[m][n][2], og = tg[m][n][3];
-          const float dht = tdh[m][n] + ht[hr + 16 * m * BH_LR + 4 * n];
-          const float ca = act_f(ACT, tc[m][n]);
-          const float dov = dht * ca;
-          const float dct = dc[m][n] + dht * og * act_dy(ACT, ca);
-          dc[m][n] = tok ? dct * fg : 0.f;
-          float z4[4];
-          z4[0] = dct * gg * ig * (1.f - ig);
-          z4[1] = dct * tcp[m][n] * fg * (1.f - fg);
-          z4[2] = dct * ig * act_dy(ACT, gg);
-          z4[3] = dov * og * (1.f - og);
-          float* zd = tok ? zt + zw + 16 * m * BZ_LR + 4 * n : trash;  // padding cells: trash row
-#pragma unroll
-          for (int k = 0; k < 4; ++k) zd[k * BZ_KQ] = z4[k];
+          const bool tok = unit_ok(w, n);
+          f32x4 z4;
+          bptt_cell<ACT>(z4, dc[m][n], tg[m][n], tc[m][n], tcp[m][n], tdh[m][n], ht[hr + 16 * m * BH_LR + 4 * n], tok,
+                         zt + zw + 16 * m * BZ_LR + 4 * n, trash);
           tc[m][n] = tcp[m][n];  // c_{t-1} is the next step's c
           const int tp = t > 0 ? t - 1 : 0;
           bwdf_tape_load(tg[m][n], tcp[m][n], tdh[m][n], rt, rdh, tl + tp * FT_STEP * 4 + ftape_slot(m, n),
@@ -582,17 +694,15 @@ lstmf_bwdp_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
                          tok && t > 0, tp > 0);
         }
       };
-      using I0 = std::integral_constant<int, 0>;
-      using I1 = std::integral_constant<int, 1>;
       for (int t = Tn - 1; t >= 0; --t) {
-        if (t < Tn - 1) store_half(I1{}, t + 1);  // rows 16..31 of dz_{t+1}: stable until P2(t)
-        half_b(I0{}, t);                          // P1(t): B(0, t)
+        if (t < Tn - 1) st.half<1, false>(zt, rz, Tn, t + 1, nr);  // rows 16..31 of dz_{t+1}: stable until P2(t)
+        half_b(I0{}, t);                                           // P1(t): B(0, t)
         lds_barrier();
-        store_half(I0{}, t);                      // rows 0..15 of dz_t: stable until P1(t - 1)
-        half_b(I1{}, t);                          // P2(t): B(1, t)
+        st.half<0, false>(zt, rz, Tn, t, nr);                      // rows 0..15 of dz_t: stable until P1(t - 1)
+        half_b(I1{}, t);                                           // P2(t): B(1, t)
         lds_barrier();
       }
-      store_half(I1{}, 0);
+      st.half<1, false>(zt, rz, Tn, 0, nr);
       __syncthreads();  // (the tiles are re-zeroed for the next row block)
     }
   }
@@ -610,9 +720,11 @@ lstmf_bwdp_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
 // halves (c, cdot and the two adjoint carries) and ONE set of step loads (gates, zdot, c_{t-1},
 // cdot_{t-1}, dH, dHd: 12 per cell): the set for the other half is issued right after a half's
 // cells, and lands while the MFMA waves finish the half-phase.
-#ifndef HFREP_TBWD_CELLGROUP
-#define HFREP_TBWD_CELLGROUP 2
-#endif
+// Cells whose temporaries share one schedule region of the cell role, in both tangent kernels: 2
+// (lstmf_tbwdp_kernel: 13.80 -> 13.45 ms per call at B = 262 144; one cell at a time was the round-4
+// schedule, seven 13.56 ms: profiles/r05_tbwd/README.md.  lstmf_tbwd1_kernel: 4 and 7 measured neutral,
+// docs/PERF.md)
+constexpr int kTanCellGroup = 2;
 template <int ACT, bool HEAD = false>
 __global__ void __launch_bounds__(512, 1)
 lstmf_tbwdp_kernel(const float* __restrict__ dH, const float* __restrict__ dHd, const float* __restrict__ tape,
@@ -633,70 +745,25 @@ lstmf_tbwdp_kernel(const float* __restrict__ dH, const float* __restrict__ dHd, 
   if (wv < 4) {
     // ---------------- MFMA role ----------------
     float ut[2][FH];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int j = 16 * (2 * w + e) + c16;
-      const bool ok = j < FH;
-#pragma unroll
-      for (int k = 0; k < FH; ++k) {
-        const float v = U[(ok ? j : 0) * FG + g * FH + k];
-        ut[e][k] = ok ? v : 0.f;
-      }
-    }
+    rev_ut_load(ut, U, w, c16, g);
     // rows of half M of (dz, dzdot) U^T, one adjoint stream after the other (8 accumulator
     // registers live: U^T takes 200 of the role's 256 VGPRs)
-    auto half_a = [&](auto MA_) {
-      constexpr int M = decltype(MA_)::value;
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-        const float* ar = (st ? zdt : zt) + (16 * M + c16) * BZ_LR + g * BZ_KQ;
-#pragma unroll
-        for (int jj = 0; jj < FH / 4; ++jj) {
-          const f32x4 a4 = *reinterpret_cast<const f32x4*>(ar + 4 * jj);
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            acc[0] = mma4(a4[s], ut[0][4 * jj + s], acc[0]);
-            acc[1] = mma4(a4[s], ut[1][4 * jj + s], acc[1]);
-          }
-          if ((jj & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-        }
-        float* hd = st ? hdt : ht;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int col = 16 * (2 * w + e) + c16;
-          if (2 * w + e < 7) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) hd[(16 * M + 4 * g + i) * BH_LR + col] = acc[e][i];
-          }
-        }
-      }
+    auto half_a = [&](auto M_) {
+      constexpr int M = decltype(M_)::value;
+      rev_half_a<M, 2>(zt, ht, ut, w, c16, g);
+      rev_half_a<M, 2>(zdt, hdt, ut, w, c16, g);
     };
     // the dz / dzdot stores ride on the MFMA role (they were 6 % of the cell role's time, which
-    // sets the half-phase length): threads 0..199 own chunk tid % 100 of rows 2 k + tid / 100; a
-    // half's rows are stable for exactly the half-phase after the one that completed them
-    const int srr = tid / 100, sch = tid - 100 * srr, sqq = sch / 25, sc = sch - 25 * sqq;
-    const int slo = (srr & 1) * BZ_LR + sqq * BZ_KQ + 4 * sc;
-    const int sgo = tid < 200 ? (srr * Tn * FG + sqq * FH + 4 * sc) * 4 : kOOB;
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
+    // sets the half-phase length)
+    const RevStore st(tid, Tn);
     for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
       const int row0 = rb * 32;
       const rsrc_t rz = ftile_rsrc(dZ, row0, B, Tn, FG), rzd = ftile_rsrc(dZd, row0, B, Tn, FG);
       const int nr = min(32, B - row0);
       auto store_half = [&](auto M_, int ts) {
         constexpr int M = decltype(M_)::value;
-#pragma unroll
-        for (int k = 8 * M; k < 8 * M + 8; ++k) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(zt + slo + 2 * k * BZ_LR);
-          const f32x4 vd = *reinterpret_cast<const f32x4*>(zdt + slo + 2 * k * BZ_LR);
-          const bool ok = 2 * k + srr < nr;
-          const int so = (2 * k * Tn + ts) * FG * 4;
-          st16(v, rz, ok, sgo, so);
-          st16(vd, rzd, ok, sgo, so);
-          if (k & 1) __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+        st.half<M, true>(zt, rz, Tn, ts, nr);
+        st.half<M, true>(zdt, rzd, Tn, ts, nr);
       };
       for (int i = tid; i < 2 * 32 * (BZ_LR + BH_LR); i += 512) zt[i] = 0.f;  // all four tiles
       __syncthreads();
@@ -713,33 +780,24 @@ lstmf_tbwdp_kernel(const float* __restrict__ dH, const float* __restrict__ dHd, 
     }
   } else {
     // ---------------- cell role ----------------
-    const int ct = tid - 256;
+    // (the c_{T-1} / cdot_{T-1} prologue stays written out: as a helper, alone on this kernel, it changed 49 of the
+    // 135 lstmf_tbwd arrays of the A/B against the parent build in their last bits,
+    // profiles/lstmf_rev_shared/single_helper.txt)
     const int ub = FUW * w + j4;
     const int hr = (4 * g + q) * BH_LR + ub, zw = (4 * g + q) * BZ_LR + ub;
-    const int srr = ct / 100, sch = ct - 100 * srr, sqq = sch / 25, sc = sch - 25 * sqq;
-    const int slo = (srr & 1) * BZ_LR + sqq * BZ_KQ + 4 * sc;
-    const int sgo = ct < 200 ? (srr * Tn * FG + sqq * FH + 4 * sc) * 4 : kOOB;
     const int tl = ftape_lane(w, lane), tcl = ftape_cell(w, lane);
     for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
       const int row0 = rb * 32;
       const rsrc_t rdh = ftile_rsrc(dH, row0, B, Tn, FH), rdhd = ftile_rsrc(dHd, row0, B, Tn, FH);
       const rsrc_t rt = ftape_rsrc(tape, rb, nrb, Tn), rtt = ftape_rsrc(ttape, rb, nrb, Tn);
-      const rsrc_t rz = ftile_rsrc(dZ, row0, B, Tn, FG), rzd = ftile_rsrc(dZd, row0, B, Tn, FG);
-      const int nr = min(32, B - row0);
       int vp1[2];
 #pragma unroll
       for (int m = 0; m < 2; ++m) vp1[m] = ((16 * m + 4 * g + q) * Tn * FH + ub) * 4;
       // HEAD: dH = hd (x) w, dHd = hdd (x) w generated per cell (a null factor: that adjoint is zero)
-      float hdv[2] = {0.f, 0.f}, hddv[2] = {0.f, 0.f};
-      const rsrc_t rhw = make_rsrc(hw, HEAD ? Tn * FH * 4 : 0);
-      if constexpr (HEAD) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          const int r = row0 + 16 * m + 4 * g + q;
-          hdv[m] = (hd && r < B) ? hd[r] : 0.f;
-          hddv[m] = (hdd && r < B) ? hdd[r] : 0.f;
-        }
-      }
+      float hdv[2], hddv[2];
+      head_rows<HEAD>(hdv, hd, hd != nullptr, row0, B, g, q);
+      head_rows<HEAD>(hddv, hdd, hdd != nullptr, row0, B, g, q);
+      const rsrc_t rhw = head_rsrc<HEAD>(hw, Tn);
       const int hvo = ub * 4;
       float tc[2][FNT], tcd[2][FNT], acn[2][FNT], acdn[2][FNT];
       f32x4 tg[FNT], tz[FNT];
@@ -750,89 +808,41 @@ lstmf_tbwdp_kernel(const float* __restrict__ dH, const float* __restrict__ dHd, 
       // (out-of-range lanes: voffset kOOB, which the range check drops whatever the soffset)
       auto load_half = [&](auto M_, int tt, bool on) {
         constexpr int m = decltype(M_)::value;
-        const int tp = tt > 0 ? tt - 1 : 0;
 #pragma unroll
         for (int n = 0; n < FNT; ++n) {
-          const bool tok = on && !(w == 3 && n >= 4);
-          const int sg = tt * FT_STEP * 4 + ftape_slot(m, n), sc = tp * FT_STEP * 4 + ftape_slot(m, n);
-          const int sd = tt * FH * 4 + 16 * n;
-          tg[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rt, tok ? tl : kOOB, sg, 0));
-          tz[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rtt, tok ? tl : kOOB, sg, 0));
-          tcp[n] = ld1(rt, (tok && tt > 0) ? tcl : kOOB, sc);
-          tcdp[n] = ld1(rtt, (tok && tt > 0) ? tcl : kOOB, sc);
-          if constexpr (HEAD) {
-            const float wv = ld1(rhw, tok ? hvo : kOOB, sd);
-            tdh[n] = hdv[m] * wv;
-            tdhd[n] = hddv[m] * wv;
-          } else {
-            tdh[n] = ld1(rdh, tok ? vp1[m] : kOOB, sd);
-            tdhd[n] = ld1(rdhd, tok ? vp1[m] : kOOB, sd);
-          }
+          const bool tok = on && unit_ok(w, n);
+          const float wn = tan_step_load<HEAD>(tg[n], tz[n], tcp[n], tcdp[n], tdh[n], rt, rtt, rdh, rhw, tl, tcl, vp1[m],
+                                               hvo, hdv[m], m, n, tt, tok);
+          if constexpr (HEAD) tdhd[n] = hddv[m] * wn;
+          else tdhd[n] = ld1(rdhd, tok ? vp1[m] : kOOB, tt * FH * 4 + 16 * n);
         }
       };
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int n = 0; n < FNT; ++n) {
-          const bool tok = !(w == 3 && n >= 4);
+          const bool tok = unit_ok(w, n);
           const int oc = tcl + (Tn - 1) * FT_STEP * 4 + ftape_slot(m, n);
           acn[m][n] = 0.f;
           acdn[m][n] = 0.f;
           tc[m][n] = ld1(rt, tok ? oc : kOOB, 0);
           tcd[m][n] = ld1(rtt, tok ? oc : kOOB, 0);
         }
-      load_half(std::integral_constant<int, 0>{}, Tn - 1, true);
+      load_half(I0{}, Tn - 1, true);
       for (int i = tid; i < 2 * 32 * (BZ_LR + BH_LR); i += 512) zt[i] = 0.f;
       __syncthreads();
       auto half_b = [&](auto M_) {
         constexpr int m = decltype(M_)::value;
 #pragma unroll
         for (int n = 0; n < FNT; ++n) {
-          const bool tok = !(w == 3 && n >= 4);
-          const float i_ = tg[n][0], f_ = tg[n][1], g_ = tg[n][2], o_ = tg[n][3];
-          const float zdi = tz[n][0], zdf = tz[n][1], zdg = tz[n][2], zdo = tz[n][3];
-          const float c = tc[m][n], cd = tcd[m][n], cp = tcp[n], cdp = tcdp[n];
-          const float si = i_ * (1.f - i_), sf = f_ * (1.f - f_), so = o_ * (1.f - o_), sg = act_dy(ACT, g_);
-          const float idot = si * zdi, fdot = sf * zdf, gdot = sg * zdg, odot = so * zdo;
-          const float ca = act_f(ACT, c), d1 = act_dy(ACT, ca), d2 = act_d2y(ACT, ca);
-          const int hi = hr + 16 * m * BH_LR + 4 * n;
-          const float a_h = tdh[n] + ht[hi], a_hd = tdhd[n] + hdt[hi];
-          const float a_od = a_hd * ca;
-          const float a_o = a_h * ca + a_hd * d1 * cd;
-          const float a_cd = acdn[m][n] + a_hd * o_ * d1;
-          const float a_c = acn[m][n] + a_h * o_ * d1 + a_hd * (odot * d1 + o_ * d2 * cd);
-          const float a_fd = a_cd * cp, a_id = a_cd * g_, a_gd = a_cd * i_;
-          const float a_f = a_c * cp + a_cd * cdp;
-          const float a_i = a_c * g_ + a_cd * gdot;
-          const float a_g = a_c * i_ + a_cd * idot;
-          acn[m][n] = tok ? a_c * f_ + a_cd * fdot : 0.f;
-          acdn[m][n] = tok ? a_cd * f_ : 0.f;
-          const float s2i = si * (1.f - 2.f * i_), s2f = sf * (1.f - 2.f * f_), s2o = so * (1.f - 2.f * o_);
-          const float s2g = act_d2y(ACT, g_);
-          float zd4[4], z4[4];
-          zd4[0] = a_id * si; zd4[1] = a_fd * sf; zd4[2] = a_gd * sg; zd4[3] = a_od * so;
-          z4[0] = a_i * si + a_id * s2i * zdi;
-          z4[1] = a_f * sf + a_fd * s2f * zdf;
-          z4[2] = a_g * sg + a_gd * s2g * zdg;
-          z4[3] = a_o * so + a_od * s2o * zdo;
-          const int zo = zw + 16 * m * BZ_LR + 4 * n;
-          float* zp = tok ? zt + zo : trash;
-          float* zdp = tok ? zdt + zo : trash;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            zp[k * BZ_KQ] = z4[k];
-            zdp[k * BZ_KQ] = zd4[k];
-          }
-          tc[m][n] = cp;
-          tcd[m][n] = cdp;
-          // HFREP_TBWD_CELLGROUP cells' temporaries per schedule region: 2 (13.80 -> 13.45 ms per call at
-          // B = 262 144; one cell at a time was the round-4 schedule, seven 13.56 ms:
-          // profiles/r05_tbwd/README.md)
-          if ((n + 1) % HFREP_TBWD_CELLGROUP == 0 || n == FNT - 1) __builtin_amdgcn_sched_barrier(0);
+          const int hi = hr + 16 * m * BH_LR + 4 * n, zo = zw + 16 * m * BZ_LR + 4 * n;
+          tan_cell<ACT, true>(acn[m][n], acdn[m][n], tg[n], tz[n], tc[m][n], tcd[m][n], tcp[n], tcdp[n], tdh[n], ht + hi,
+                              tdhd[n], hdt + hi, unit_ok(w, n), zt, zdt, zo, trash);
+          tc[m][n] = tcp[n];
+          tcd[m][n] = tcdp[n];
+          if ((n + 1) % kTanCellGroup == 0 || n == FNT - 1) __builtin_amdgcn_sched_barrier(0);
         }
       };
-      using I0 = std::integral_constant<int, 0>;
-      using I1 = std::integral_constant<int, 1>;
       for (int t = Tn - 1; t >= 0; --t) {
         half_b(I0{});                             // P1(t): B(0, t)
         __builtin_amdgcn_sched_barrier(0);        //   (the load set is free only after the cells)
@@ -861,12 +871,6 @@ lstmf_tbwdp_kernel(const float* __restrict__ dH, const float* __restrict__ dHd, 
 // role issues 200 exact-fp32 MFMAs per half-phase (dz U^T only) and stores dZ, the cell role carries three
 // values per cell and half (c, cdot via the tapes, the two carries) and one set of step loads (gates, zdot,
 // c_{t-1}, cdot_{t-1}, dH, aH).  dH / the head factor hd may be null (no primal seed).
-#ifndef HFREP_TBWD1_CELLGROUP
-#define HFREP_TBWD1_CELLGROUP 2  // cells per schedule region of the cell role, as in lstmf_tbwdp_kernel
-#endif
-#ifndef HFREP_TBWD1_EARLYLOAD
-#define HFREP_TBWD1_EARLYLOAD 1  // 0: the cell role's loads after the last cell of a half (A/B: docs/PERF.md)
-#endif
 template <int ACT, bool HEAD = false>
 __global__ void __launch_bounds__(512, 1)
 lstmf_tbwd1_kernel(const float* __restrict__ dH, const float* __restrict__ aH, const float* __restrict__ tape,
@@ -884,76 +888,30 @@ lstmf_tbwd1_kernel(const float* __restrict__ dH, const float* __restrict__ aH, c
   if (wv < 4) {
     // ---------------- MFMA role ----------------
     float ut[2][FH];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int j = 16 * (2 * w + e) + c16;
-      const bool ok = j < FH;
-#pragma unroll
-      for (int k = 0; k < FH; ++k) {
-        const float v = U[(ok ? j : 0) * FG + g * FH + k];
-        ut[e][k] = ok ? v : 0.f;
-      }
-    }
-    // rows of half M of dz U^T -> the dh tile
-    auto half_a = [&](auto MA_) {
-      constexpr int M = decltype(MA_)::value;
-      f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      const float* ar = zt + (16 * M + c16) * BZ_LR + g * BZ_KQ;
-#pragma unroll
-      for (int jj = 0; jj < FH / 4; ++jj) {
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(ar + 4 * jj);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          acc[0] = mma4(a4[s], ut[0][4 * jj + s], acc[0]);
-          acc[1] = mma4(a4[s], ut[1][4 * jj + s], acc[1]);
-        }
-        if ((jj & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int col = 16 * (2 * w + e) + c16;
-        if (2 * w + e < 7) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) ht[(16 * M + 4 * g + i) * BH_LR + col] = acc[e][i];
-        }
-      }
-    };
-    // the dz stores ride on the MFMA role: threads 0..199 own chunk tid % 100 of rows 2 k + tid / 100; a
-    // half's rows are stable for exactly the half-phase after the one that completed them
-    const int srr = tid / 100, sch = tid - 100 * srr, sqq = sch / 25, sc = sch - 25 * sqq;
-    const int slo = (srr & 1) * BZ_LR + sqq * BZ_KQ + 4 * sc;
-    const int sgo = tid < 200 ? (srr * Tn * FG + sqq * FH + 4 * sc) * 4 : kOOB;
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
+    rev_ut_load(ut, U, w, c16, g);
+    const RevStore st(tid, Tn);  // the dz stores ride on the MFMA role
     for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
       const int row0 = rb * 32;
       const rsrc_t rz = ftile_rsrc(dZ, row0, B, Tn, FG);
       const int nr = min(32, B - row0);
-      auto store_half = [&](auto M_, int ts) {
-        constexpr int M = decltype(M_)::value;
-#pragma unroll
-        for (int k = 8 * M; k < 8 * M + 8; ++k) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(zt + slo + 2 * k * BZ_LR);
-          st16(v, rz, 2 * k + srr < nr, sgo, (2 * k * Tn + ts) * FG * 4);
-          if (k & 1) __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      };
       for (int i = tid; i < 32 * (BZ_LR + BH_LR); i += 512) zt[i] = 0.f;  // both tiles
       __syncthreads();
       for (int t = Tn - 1; t >= 0; --t) {
-        if (t < Tn - 1) store_half(I1{}, t + 1);  // rows 16..31 of dz_{t+1}: stable during P1(t)
-        half_a(I1{});
+        if (t < Tn - 1) st.half<1, true>(zt, rz, Tn, t + 1, nr);  // rows 16..31 of dz_{t+1}: stable during P1(t)
+        rev_half_a<1, 2>(zt, ht, ut, w, c16, g);
         lds_barrier();
-        store_half(I0{}, t);                      // rows 0..15 of dz_t: stable during P2(t)
-        half_a(I0{});
+        st.half<0, true>(zt, rz, Tn, t, nr);                      // rows 0..15 of dz_t: stable during P2(t)
+        rev_half_a<0, 2>(zt, ht, ut, w, c16, g);
         lds_barrier();
       }
-      store_half(I1{}, 0);
+      st.half<1, true>(zt, rz, Tn, 0, nr);
       __syncthreads();
     }
   } else {
     // ---------------- cell role ----------------
+    // (written out here: the cell adjoint -- tan_cell<ACT, false> alone on this kernel changed 15 of the 108
+    // lstmf_tbwd1 arrays of the A/B against the parent build in their last bits -- and the prologue, 56 of 108:
+    // profiles/lstmf_rev_shared/single_helper.txt)
     const int ub = FUW * w + j4;
     const int hr = (4 * g + q) * BH_LR + ub, zw = (4 * g + q) * BZ_LR + ub;
     const int tl = ftape_lane(w, lane), tcl = ftape_cell(w, lane);
@@ -965,15 +923,9 @@ lstmf_tbwd1_kernel(const float* __restrict__ dH, const float* __restrict__ aH, c
 #pragma unroll
       for (int m = 0; m < 2; ++m) vp1[m] = ((16 * m + 4 * g + q) * Tn * FH + ub) * 4;
       // HEAD: dH = hd (x) w generated per cell (a null factor: the primal seed is zero)
-      float hdv[2] = {0.f, 0.f};
-      const rsrc_t rhw = make_rsrc(hw, HEAD ? Tn * FH * 4 : 0);
-      if constexpr (HEAD) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          const int r = row0 + 16 * m + 4 * g + q;
-          hdv[m] = (hd && r < B) ? hd[r] : 0.f;
-        }
-      }
+      float hdv[2];
+      head_rows<HEAD>(hdv, hd, hd != nullptr, row0, B, g, q);
+      const rsrc_t rhw = head_rsrc<HEAD>(hw, Tn);
       const int hvo = ub * 4;
       float tc[2][FNT], tcd[2][FNT], acn[2][FNT], acdn[2][FNT];
       f32x4 tg[FNT], tz[FNT];
@@ -984,17 +936,10 @@ lstmf_tbwd1_kernel(const float* __restrict__ dH, const float* __restrict__ aH, c
       // (out-of-range lanes: voffset kOOB, which the range check drops whatever the soffset)
       auto load_cell = [&](auto M_, int n, int tt, bool on) {
         constexpr int m = decltype(M_)::value;
-        const int tp = tt > 0 ? tt - 1 : 0;
-        const bool tok = on && !(w == 3 && n >= 4);
-        const int sg = tt * FT_STEP * 4 + ftape_slot(m, n), sc = tp * FT_STEP * 4 + ftape_slot(m, n);
-        const int sd = tt * FH * 4 + 16 * n;
-        tg[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rt, tok ? tl : kOOB, sg, 0));
-        tz[n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rtt, tok ? tl : kOOB, sg, 0));
-        tcp[n] = ld1(rt, (tok && tt > 0) ? tcl : kOOB, sc);
-        tcdp[n] = ld1(rtt, (tok && tt > 0) ? tcl : kOOB, sc);
-        if constexpr (HEAD) tdh[n] = hdv[m] * ld1(rhw, tok ? hvo : kOOB, sd);
-        else tdh[n] = ld1(rdh, tok ? vp1[m] : kOOB, sd);
-        tah[n] = ld1(rah, tok ? vp1[m] : kOOB, sd);
+        const bool tok = on && unit_ok(w, n);
+        tan_step_load<HEAD>(tg[n], tz[n], tcp[n], tcdp[n], tdh[n], rt, rtt, rdh, rhw, tl, tcl, vp1[m], hvo, hdv[m], m, n, tt,
+                            tok);
+        tah[n] = ld1(rah, tok ? vp1[m] : kOOB, tt * FH * 4 + 16 * n);
       };
       auto load_half = [&](auto M_, int tt, bool on) {
 #pragma unroll
@@ -1004,25 +949,25 @@ lstmf_tbwd1_kernel(const float* __restrict__ dH, const float* __restrict__ aH, c
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int n = 0; n < FNT; ++n) {
-          const bool tok = !(w == 3 && n >= 4);
+          const bool tok = unit_ok(w, n);
           const int oc = tcl + (Tn - 1) * FT_STEP * 4 + ftape_slot(m, n);
           acn[m][n] = 0.f;
           acdn[m][n] = 0.f;
           tc[m][n] = ld1(rt, tok ? oc : kOOB, 0);
           tcd[m][n] = ld1(rtt, tok ? oc : kOOB, 0);
         }
-      load_half(std::integral_constant<int, 0>{}, Tn - 1, true);
+      load_half(I0{}, Tn - 1, true);
       for (int i = tid; i < 32 * (BZ_LR + BH_LR); i += 512) zt[i] = 0.f;
       __syncthreads();
       // cells of half M.  Each cell issues the loads of the set's next use (half MN at step tn) right after its
       // own math, as lstmf_bwds_kernel's cells do: with half the matrix work the cell role waits on its loads,
-      // not on the MFMA role (HFREP_TBWD1_EARLYLOAD=0: all seven after the last cell, lstmf_tbwdp_kernel's order,
-      // +6 % per call; a second register set for the 16-byte loads spills: docs/PERF.md)
+      // not on the MFMA role (all seven after the last cell, lstmf_tbwdp_kernel's order, was measured +6 % per
+      // call; a second register set for the 16-byte loads spills: docs/PERF.md)
       auto half_b = [&](auto M_, auto MN_, int tn, bool non) {
         constexpr int m = decltype(M_)::value;
 #pragma unroll
         for (int n = 0; n < FNT; ++n) {
-          const bool tok = !(w == 3 && n >= 4);
+          const bool tok = unit_ok(w, n);
           const float i_ = tg[n][0], f_ = tg[n][1], g_ = tg[n][2], o_ = tg[n][3];
           const float zdi = tz[n][0], zdf = tz[n][1], zdg = tz[n][2], zdo = tz[n][3];
           const float c = tc[m][n], cd = tcd[m][n], cp = tcp[n], cdp = tcdp[n];
@@ -1052,13 +997,10 @@ lstmf_tbwd1_kernel(const float* __restrict__ dH, const float* __restrict__ aH, c
           for (int k = 0; k < 4; ++k) zp[k * BZ_KQ] = z4[k];
           tc[m][n] = cp;
           tcd[m][n] = cdp;
-          if constexpr (HFREP_TBWD1_EARLYLOAD) load_cell(MN_, n, tn, non);
-          if ((n + 1) % HFREP_TBWD1_CELLGROUP == 0 || n == FNT - 1) __builtin_amdgcn_sched_barrier(0);
+          load_cell(MN_, n, tn, non);
+          if ((n + 1) % kTanCellGroup == 0 || n == FNT - 1) __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (!HFREP_TBWD1_EARLYLOAD) load_half(MN_, tn, non);
       };
-      using I0 = std::integral_constant<int, 0>;
-      using I1 = std::integral_constant<int, 1>;
       for (int t = Tn - 1; t >= 0; --t) {
         half_b(I0{}, I1{}, t, true);                        // P1(t): B(0, t), then half 1's loads for P2(t)
         lds_barrier();
@@ -1386,13 +1328,8 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
   const int hr = (4 * g + q) * BH_LR + ub, zw = (4 * g + q) * BZ_LR + ub;  // (+16 m rows, + 4 n units)
   const int zpw = ((4 * g + q) * BS_LZ + 4 * ub) * 2;                    // plane word (+ 32 n bytes)
   const int ao = (c16 * BS_LZ + 8 * g) * 2;  // A fragment: row c16 (+ 16 M), k = 32 ks + 8 g .. + 7
-  // dZ store share: threads 0..199 own chunk tid % 100 of rows 2 k + tid / 100 (k < 16)
-  const int srr = tid / 100, sch = tid - 100 * srr, sqq = sch / 25, sc = sch - 25 * sqq;
-  const int slo = (srr & 1) * BZ_LR + sqq * BZ_KQ + 4 * sc;
-  const int sgo = tid < 200 ? (srr * Tn * FG + sqq * FH + 4 * sc) * 4 : kOOB;
+  const RevStore st(tid, Tn);
   const int tl = ftape_lane(w, lane), tcl = ftape_cell(w, lane);
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
   for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
     const int row0 = rb * 32;
     const rsrc_t rdh = ftile_rsrc(dH, row0, B, Tn, FH), rt = ftape_rsrc(tape, rb, nrb, Tn);
@@ -1403,15 +1340,9 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
 #pragma unroll
     for (int m = 0; m < 2; ++m) vp1[m] = ((16 * m + 4 * g + q) * Tn * FH + ub) * 4;
     // HEAD: the lane rows' head adjoint factors d[row] (0 past B) and the head weight's descriptor
-    float hdv[2] = {0.f, 0.f};
-    const rsrc_t rhw = make_rsrc(hw, HEAD ? Tn * FH * 4 : 0);
-    if constexpr (HEAD) {
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const int r = row0 + 16 * m + 4 * g + q;
-        hdv[m] = r < B ? hd[r] : 0.f;
-      }
-    }
+    float hdv[2];
+    head_rows<HEAD>(hdv, hd, true, row0, B, g, q);  // (the launcher selects HEAD by hd)
+    const rsrc_t rhw = head_rsrc<HEAD>(hw, Tn);
     const int hvo = ub * 4;
     float dc[2][FNT], tc[2][FNT];
     f32x4 tg[FNT];
@@ -1419,7 +1350,7 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
     const int T1 = Tn - 1;
 #pragma unroll
     for (int n = 0; n < FNT; ++n) {
-      const bool tok = !(w == 3 && n >= 4);
+      const bool tok = unit_ok(w, n);
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
         dc[m][n] = 0.f;
@@ -1434,33 +1365,15 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
       reinterpret_cast<__attribute__((address_space(3))) u32x4_t*>(zp)[i] = u32x4_t{0, 0, 0, 0};
     for (int i = tid; i < 32 * BH_LR; i += 256) ht[i] = 0.f;
     __syncthreads();
-    // rows of half M of the fp32 dz tile (dz at step ts) -> dZ[:, ts, :]
-    auto store_half = [&](auto M_, int ts) {
-      constexpr int M = decltype(M_)::value;
-#pragma unroll
-      for (int k = 8 * M; k < 8 * M + 8; ++k) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(zt + slo + 2 * k * BZ_LR);
-        st16(v, rz, 2 * k + srr < nr, sgo, (2 * k * Tn + ts) * FG * 4);
-      }
-    };
     // cell adjoint of (row half M, unit tile n) at step t, then the loads for the set's next use
     auto cell = [&](auto M_, int n, float hrec, int t) {
       constexpr int m = decltype(M_)::value;
-      const bool tok = !(w == 3 && n >= 4);
-      const float ig = tg[n][0], fg = tg[n][1], gg = tg[n][2], og = tg[n][3];
-      const float dht = tdh[n] + hrec;
-      const float ca = act_f(ACT, tc[m][n]);
-      const float dov = dht * ca;
-      const float dct = dc[m][n] + dht * og * act_dy(ACT, ca);
-      dc[m][n] = tok ? dct * fg : 0.f;
+      const bool tok = unit_ok(w, n);
       f32x4 z4;
-      z4[0] = dct * gg * ig * (1.f - ig);
-      z4[1] = dct * tcp[n] * fg * (1.f - fg);
-      z4[2] = dct * ig * act_dy(ACT, gg);
-      z4[3] = dov * og * (1.f - og);
-      float* zd = tok ? zt + zw + 16 * m * BZ_LR + 4 * n : trash;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) zd[k * BZ_KQ] = z4[k];
+      const float dht = bptt_cell<ACT>(z4, dc[m][n], tg[n], tc[m][n], tcp[n], tdh[n], hrec, tok,
+                                       zt + zw + 16 * m * BZ_LR + 4 * n, trash);
+      // (the plane split and store after the fp32 words, the AHD store last: this statement order keeps the
+      // twelve kernels' instruction streams, profiles/lstmf_grad_split/README.md)
       uint32_t p[3][2];
       split3(z4, p);
       planes_store(p, tok ? zp + zpw + 16 * m * BS_LZ * 2 + 32 * n : trashp, tok ? BS_PL : 0);
@@ -1482,10 +1395,11 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
     // dh_rec = dz[rows MA] U^T (the planes hold dz_{t + 1} there for MA = 1, dz_t for MA = 0)
     auto phase = [&](auto MA_, int t) {
       constexpr int MA = decltype(MA_)::value;
+      // rows of half MA of the fp32 dz tile -> dZ
       if constexpr (MA == 1) {
-        if (t < T1) store_half(I1{}, t + 1);
+        if (t < T1) st.half<1, false>(zt, rz, Tn, t + 1, nr);
       } else {
-        store_half(I0{}, t);
+        st.half<0, false>(zt, rz, Tn, t, nr);
       }
       float hv[FNT];  // the cells' dh_rec words (rows of half 1 - MA, completed in the previous phase)
 #pragma unroll
@@ -1535,7 +1449,7 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
       phase(I1{}, t);  // P1(t): B(0, t) + A(1, t)
       phase(I0{}, t);  // P2(t): B(1, t) + A(0, t - 1)
     }
-    store_half(I1{}, 0);
+    st.half<1, false>(zt, rz, Tn, 0, nr);
     __syncthreads();  // (the tiles are re-zeroed for the next row block)
   }
 }

@@ -1,7 +1,7 @@
 """Microbenchmark of the LSTM v2 recurrent kernels (fwd / tangent fwd / BPTT / tangent reverse).
 
 Times each layer-level op at the flagship shape (H=100, T=24, bf16) and prints one JSON line per op.
-Usage: python scripts/bench_lstm.py [--batch 16384] [--K 100] [--iters 10] [--only fwd,bwd,...]
+Usage: python scripts/bench_lstm.py [--batch 16384] [--K 100] [--iters 10] [--repeats 1] [--only fwd,bwd,tbwd1,...]
 """
 import argparse
 import json
@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--K", type=int, default=100)
     ap.add_argument("--act", type=int, default=2)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=1, help="timed repeats per op (one JSON line each)")
     ap.add_argument("--only", default="fwd,tfwd,bwd,tbwd,bwd_dx,tbwd_dx,dgrad")
     ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float32"])
     a = ap.parse_args()
@@ -64,10 +65,14 @@ def main():
         "wgrad": lambda: Fn.lstm_wgrad_(x, hs, dZ_, gW, gU, gb),
         "wgrad_tan": lambda: Fn.lstm_wgrad_(x, hs, dZ_, gW, gU, gb, xd, hds, dZ_),
     }
+    if "tbwd1" in a.only.split(","):  # fp32 only: the single-stream tangent reverse, a_hd from a kept BPTT
+        ahd = Fn.lstm_layer_bwd_keep(dHd, tape, U, a.act)[2]
+        ops["tbwd1"] = lambda: Fn.lstm_layer_tbwd1(dH, ahd, tape, ttape, U, a.act)
     for name in a.only.split(","):
-        ms = timeit(ops[name], a.iters)
-        print(json.dumps({"op": name, "dtype": a.dtype, "B": B, "T": T, "K": K, "ms": round(ms, 4),
-                          "us_per_step": round(ms * 1e3 / T, 2)}), flush=True)
+        for _ in range(a.repeats):
+            ms = timeit(ops[name], a.iters)
+            print(json.dumps({"op": name, "dtype": a.dtype, "B": B, "T": T, "K": K, "ms": round(ms, 4),
+                              "us_per_step": round(ms * 1e3 / T, 2)}), flush=True)
 
 
 if __name__ == "__main__":

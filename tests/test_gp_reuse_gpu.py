@@ -127,6 +127,28 @@ def test_single_stream_bitwise_run_to_run(cuda):
     _close(runs[0], ref[(False, True)])
 
 
+def test_row_block_setup_over_many_tiles(cuda):
+    """More 32-row tiles than workgroups (B = 256 * 32 + 45, T = 2, tanh), so every workgroup walks several
+    tiles and the per-row-block set-up of the reverse kernels (HEAD row factors, descriptors, prologue loads,
+    store share) runs more than once: the BPTT with HEAD and the h adjoints kept (dZ and a_hd) and the
+    single-stream tangent reverse with HEAD, fed by that a_hd, against fp64 at the suite's fp32 tolerance;
+    every output bitwise equal on a second run."""
+    B, T, act = 256 * 32 + 45, 2, 2
+    p, ref = _point(B, T, act)
+    dev = {k: v.to(cuda) for k, v in p.items()}
+    _, tape = Fn.lstm_layer_fwd(dev["x"], dev["W"], dev["b"], dev["U"], act, True)
+    _, ttape = Fn.lstm_layer_tfwd(dev["xd"], dev["W"], tape, dev["U"], act)
+    o1 = Fn.OuterAdjoint(dev["d1"], dev["w"], (B, T, H))
+    o2 = Fn.OuterAdjoint(dev["d2"], dev["w"], (B, T, H))
+    (dZ, _, ahd), (dZ2, _, ahd2) = (Fn.lstm_layer_bwd_keep(o2, tape, dev["U"], act) for _ in range(2))
+    _close(dZ, ref[("dzd", True)])
+    _close(ahd, ref[("ahd", True)])
+    assert torch.equal(dZ, dZ2) and torch.equal(ahd, ahd2)
+    t1, t2 = (Fn.lstm_layer_tbwd1(o1, ahd, tape, ttape, dev["U"], act) for _ in range(2))
+    _close(t1, ref[(True, True)])
+    assert torch.equal(t1, t2)
+
+
 class _OpLog:
     """torch.ops.hfrep with every op call's name recorded (one native op = one kernel family)."""
 
