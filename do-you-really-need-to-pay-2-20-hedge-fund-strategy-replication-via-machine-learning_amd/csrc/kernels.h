@@ -68,9 +68,10 @@ bool launch_lstmf_tbwd1(const float* dH, const float* aH, const float* tape, con
 bool launch_lstmf_tbwd(const float* dH, const float* dHd, const float* tape, const float* ttape, const float* U, float* dZ,
                        float* dZd, int B, int Tn, int H, int act, hipStream_t s, const float* hd = nullptr,
                        const float* hdd = nullptr, const float* hw = nullptr);
-// forward kernel selection: 1 = exact-fp32 everywhere, 2 = split recurrent product for K <= 36 (default);
-// returns the previous setting
-int set_lstmf_fwd_impl(int v);  // 1: exact-fp32 forward everywhere, 2: the split-recurrent one for K <= 36
+// forward kernel selection: 1 = exact-fp32 everywhere, 2 = split recurrent product for K <= 36 on four waves,
+// 3 = the same on eight waves, two per SIMD, where instantiated (K = 32; bitwise equal to 2, which the other
+// K <= 36 take; default); returns the previous setting
+int set_lstmf_fwd_impl(int v);  // 1: exact-fp32 forward everywhere, 2 / 3: the split-recurrent one for K <= 36
 int set_lstmf_bwd_impl(int v);  // 2: the exact-fp32 BPTT kernel, 3: the split-recurrent one
 
 // ---- lstmf_grad.hip (fp32 LSTM gradient GEMMs; shared device helpers: lstmf_dev.h) ----

@@ -1260,6 +1260,304 @@ lstmf_fwds_kernel(const float* __restrict__ x, const float* __restrict__ W, cons
 }
 
 // ------------------------------------------------------------------------------------------
+// The split forward on 8 waves, two per SIMD: lstmf_fwds2_kernel
+// ------------------------------------------------------------------------------------------
+// lstmf_fwds_kernel runs one wave per SIMD, and each wave alternates an MFMA chain (one row half of its 7
+// tiles) with that half's gate math: the matrix pipe idles during the gate math and the VALU during the
+// chain.  Here the 25 real gate-interleaved tiles (units 4 gt .. 4 gt + 3 for tile gt; the 3 padding tiles
+// of the 4-wave layout are gone) go to 8 waves by columns, wave 0 tiles 0..3 and wave v > 0 tiles 3 v + 1 ..
+// 3 v + 3, so the two waves v, v + 4 of a SIMD carry 7 / 6 / 6 / 6 tiles and the hardware interleaves one
+// wave's gate math with the other's MFMAs.  256 registers per wave: U's planes stay pinned (36 per tile),
+// W^T moves to LDS (25 tiles x 2 x 1 KiB, one ds_read_b128 per tile and four k-steps, read per row half
+// like lstmf_fwd_kernel's wl).  The per-tile arithmetic, its order and the addresses are lstmf_fwds_kernel's
+// -- tile gt is tile gt % 7 of wave gt / 7 there -- so hs, both tapes and hds are bitwise that kernel's.
+// Each tile count is its own straight-line instantiation behind one branch on the wave index at kernel
+// entry (no wave-uniform tile guard between an MFMA and the read of its result).
+// SKEW, how the two waves of a SIMD get out of phase after the step barrier (bit 0: waves 4..7 run their
+// MFMA chains at s_setprio 1; bit 1: waves 4..7 take the row halves in the opposite order).  Both measured
+// neutral or slower than plain age arbitration (profiles/fwd_two_wave/README.md), so the knob is off.
+#ifndef HFREP_FWDS2_SKEW
+#define HFREP_FWDS2_SKEW 0
+#endif
+constexpr int F2_TILES = 25;
+// a product rounded to fp32 on its own: opaque to the compiler, so -ffp-contract=fast cannot fuse it into a
+// neighbouring add (explicit fmaf calls are the only fused operations of the cell math below)
+__device__ __forceinline__ float f2_rnd(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+template <int KX>
+constexpr size_t fwds2_smem() {
+  return (size_t)(2 * 32 * FGeo<KX>::LR + 4) * 4 + 2 * FS_HB + (size_t)F2_TILES * FGeo<KX>::NJ * 64 * 16;
+}
+
+template <int ACT, int KX, bool TAPE, bool TAN, int NT, bool HI, bool FLIP>
+__device__ __forceinline__ void fwds2_run(const float* __restrict__ x, const float* __restrict__ W,
+                                          const float* __restrict__ bias, const float* __restrict__ U,
+                                          const float* __restrict__ ptape, float* __restrict__ hs,
+                                          float* __restrict__ tape, int B, int Tn, float* fsm, int v) {
+  using GX = FGeo<KX>;
+  float* xb = fsm;                                                 // [2][32 * LRX] fp32, K-permuted
+  float* trash = xb + 2 * 32 * GX::LR;                              // [4] out-of-range writes
+  lds_char* hb = (lds_char*)(trash + 4);                            // [2][FS_HB] h planes + tail
+  f32x4* wl = (f32x4*)(hb + 2 * FS_HB);                             // [25 tiles][NJ][64 lanes] W^T k-steps 4 j .. 4 j + 3
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int q = lane & 3, g = lane >> 4, j4 = (lane & 15) >> 2;
+  const int t0 = v ? 3 * v + 1 : 0;  // first tile of this wave (uniform)
+  const int ub = 4 * t0 + j4;        // unit of tile 0 in this lane's MFMA column; tile n adds 4 n
+  const int nrb = (B + 31) / 32;
+  const int flip = (FLIP && v >= 4) ? 1 : 0;
+
+  for (int i = tid; i < 2 * 32 * GX::LR; i += 512) xb[i] = 0.f;
+
+  constexpr float GSC = ACT == ACT_TANH ? -2.f * kLog2e : ACT == ACT_SIGMOID ? -kLog2e : 1.f;
+  const float sc = TAN ? 1.f : (q == 2 ? GSC : -kLog2e);
+  bf16x8 up[3][NT][3];
+  float ut[NT], bq[NT];
+  int tsl[NT];  // tape slot of tile n, row half 0: the 4-wave kernel's (w, n) = (gt / 7, gt % 7) (bytes, uniform)
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const int cl = q * FH + ub + 4 * n;  // < 400: every tile is real
+    tsl[n] = ftape_lane((t0 + n) / FNT, 0) + (((t0 + n) % FNT) * FT_SLOT) * 4;
+#pragma unroll
+    for (int ks = 0; ks < 3; ++ks) {
+      uint32_t hh[8], mm[8], ll[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = 32 * ks + 8 * g + j;  // < 96
+        const float u_ = f2_rnd(U[k * FG + cl] * sc);  // (rounded before the split, as there)
+        const uint32_t h = trunc_hi(u_);
+        const float r1 = u_ - __builtin_bit_cast(float, h);
+        const uint32_t m = trunc_hi(r1);
+        const float r2 = r1 - __builtin_bit_cast(float, m);
+        hh[j] = h; mm[j] = m; ll[j] = __builtin_bit_cast(uint32_t, r2);
+      }
+      uint4 ph, pm, pl;
+      ph.x = __builtin_amdgcn_perm(hh[1], hh[0], 0x07060302u); ph.y = __builtin_amdgcn_perm(hh[3], hh[2], 0x07060302u);
+      ph.z = __builtin_amdgcn_perm(hh[5], hh[4], 0x07060302u); ph.w = __builtin_amdgcn_perm(hh[7], hh[6], 0x07060302u);
+      pm.x = __builtin_amdgcn_perm(mm[1], mm[0], 0x07060302u); pm.y = __builtin_amdgcn_perm(mm[3], mm[2], 0x07060302u);
+      pm.z = __builtin_amdgcn_perm(mm[5], mm[4], 0x07060302u); pm.w = __builtin_amdgcn_perm(mm[7], mm[6], 0x07060302u);
+      pl.x = __builtin_amdgcn_perm(ll[1], ll[0], 0x07060302u); pl.y = __builtin_amdgcn_perm(ll[3], ll[2], 0x07060302u);
+      pl.z = __builtin_amdgcn_perm(ll[5], ll[4], 0x07060302u); pl.w = __builtin_amdgcn_perm(ll[7], ll[6], 0x07060302u);
+      up[ks][n][0] = __builtin_bit_cast(bf16x8, ph);
+      up[ks][n][1] = __builtin_bit_cast(bf16x8, pm);
+      up[ks][n][2] = __builtin_bit_cast(bf16x8, pl);
+      // (no AGPR pin: a kernel that names AGPRs gets its 256 registers as 128 V + 128 A and spills)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) asm volatile("" : "+v"(up[ks][n][p]));
+    }
+    ut[n] = U[(96 + g) * FG + cl] * sc;
+#pragma unroll
+    for (int j = 0; j < GX::NJ; ++j) {
+      f32x4 wv;
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) {
+        const int k = 4 * (4 * j + s4) + g;
+        const float w_ = W[min(k, KX - 1) * FG + cl];
+        wv[s4] = k < KX ? w_ * sc : 0.f;
+      }
+      wl[((t0 + n) * GX::NJ + j) * 64 + lane] = wv;
+    }
+    const float bv = bias ? bias[cl] : 0.f;
+    bq[n] = !TAN ? f2_rnd(bv * sc) : 0.f;
+  }
+  const bool glin = !TAN && ACT == ACT_LINEAR && q == 2;
+  const float am = (ACT == ACT_TANH && q == 2) ? 2.f : 1.f, bm = (ACT == ACT_TANH && q == 2) ? -1.f : 0.f;
+  const int ax = (lane & 15) * GX::LR + g * GX::KQ;
+  const int ahp = ((lane & 15) * FS_HR + 8 * g) * 2, aht = 3 * FS_HPL + ((lane & 15) * 4 + g) * 4;
+  const f32x4* wlw = wl + t0 * GX::NJ * 64 + lane;
+  // x_t: the 256 threads of waves 4..7 (the 3-tile waves) load and stage it; the others write the trash word
+  FXPart<KX> xp;
+  const bool xld = v >= 4;
+
+  for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const int row0 = rb * 32;
+    const rsrc_t rx = ftile_rsrc(x, row0, B, Tn, KX);
+    const rsrc_t rh = ftile_rsrc(hs, row0, B, Tn, FH);
+    const rsrc_t rt = ftape_rsrc(TAPE ? tape : nullptr, rb, nrb, Tn);
+    const rsrc_t rp = ftape_rsrc(TAN ? ptape : nullptr, rb, nrb, Tn);
+    const int vp0 = ((4 * g + q) * Tn * FH + ub) * 4;  // (row 4 g + q, unit ub) in (B,T,H); row half m adds 16 rows
+    float cprev[TAN ? 2 : 1][NT];
+    if constexpr (TAN) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) cprev[i][n] = 0.f;
+    }
+    float cst[2][NT];  // [i]: the row half this wave takes i-th (half i ^ flip)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) cst[i][n] = 0.f;
+    xp.set(Tn, tid & 255);
+    if (!xld) {
+#pragma unroll
+      for (int j = 0; j < FXPart<KX>::NJ; ++j) { xp.goff[j] = kOOB; xp.lpos[j] = -1; }
+    }
+    xp.load(rx, Tn, 0, true);
+    for (int i = tid; i < FS_HB / 16; i += 512)
+      reinterpret_cast<__attribute__((address_space(3))) u32x4_t*>(hb)[i] = u32x4_t{0, 0, 0, 0};
+    xp.to_lds(xb, trash);
+    __syncthreads();
+    for (int t = 0; t < Tn; ++t) {
+      const float* xcur = xb + (t & 1) * 32 * GX::LR;
+      const lds_char* hcur = hb + (t & 1) * FS_HB;
+      lds_char* hnext = hb + ((t + 1) & 1) * FS_HB;
+      xp.load(rx, Tn, t + 1, t + 1 < Tn);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int m = i ^ flip;  // (uniform)
+        f32x4 pg[TAN ? NT : 1];
+        float pc[TAN ? NT : 1];
+        const int p1 = vp0 + (16 * m * Tn + t) * FH * 4;
+        const int tb = t * FT_STEP * 4 + m * ftape_slot(1, 0);  // (uniform)
+        if constexpr (TAN) {
+#pragma unroll
+          for (int n = 0; n < NT; ++n) {
+            pg[n] = ld4(rp, lane * 16 + (tb + tsl[n]));
+            pc[n] = ld1(rp, (256 + lane) * 4 + (tb + tsl[n]), 0);
+          }
+        }
+        f32x4 acc[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (HI) __builtin_amdgcn_s_setprio(1);
+        // ---- z = x_t W (exact fp32) ----
+#pragma unroll
+        for (int j = 0; j < GX::NJ; ++j) {
+          const f32x4 a4 = *reinterpret_cast<const f32x4*>(xcur + ax + 16 * m * GX::LR + 4 * j);
+          f32x4 w4[NT];
+#pragma unroll
+          for (int n = 0; n < NT; ++n) w4[n] = wlw[(n * GX::NJ + j) * 64];
+#pragma unroll
+          for (int s4 = 0; s4 < 4; ++s4) {
+            const int ks = 4 * j + s4;
+            if (ks >= GX::KS) break;
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[n] = mma4(a4[s4], w4[n][s4], acc[n]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        // ---- + h_{t-1} U: the split k < 96 and the exact fp32 tail, chained into acc ----
+#pragma unroll
+        for (int ks = 0; ks < 3; ++ks) {
+          const lds_char* ar = hcur + ahp + 16 * m * FS_HR * 2 + 64 * ks;
+          const bf16x8 a[3] = {*reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(ar),
+                               *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(ar + FS_HPL),
+                               *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(ar + 2 * FS_HPL)};
+#pragma unroll
+          for (int n = 0; n < NT; ++n) acc[n] = mma_split6(a, up[ks][n], acc[n]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        {
+          const float at = *reinterpret_cast<const __attribute__((address_space(3))) float*>(hcur + aht + 16 * m * 16);
+#pragma unroll
+          for (int n = 0; n < NT; ++n) acc[n] = mma4(at, ut[n], acc[n]);
+        }
+        if constexpr (HI) __builtin_amdgcn_s_setprio(0);
+        // ---- gate math, cell update, stores (row 16 m + 4 g + q, unit ub + 4 n after the transpose) ----
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          // Every product-sum below is written out, fused (fmaf) or rounded (f2_rnd), as the compiler
+          // contracted it in lstmf_fwds_kernel.  That differs between that kernel's tiles n < 4 and n >= 4 (the
+          // latter sit behind the padded-unit select): fa picks the form of this tile's owner there.
+          const int v1 = p1 + 16 * n;
+          const int tg = lane * 16 + (tb + tsl[n]), tc = (256 + lane) * 4 + (tb + tsl[n]);
+          const bool fa = (t0 + n) % FNT < 4;  // (uniform)
+          const f32x4 zs = acc[n];
+          float hv, hr;  // h (or hdot) and its residual below the high bf16 plane
+          if constexpr (!TAN) {
+            float y[4];
+#pragma unroll
+            for (int e4 = 0; e4 < 4; ++e4) {
+              const float s_ = zs[e4] + bq[n];
+              const float e = __builtin_fmaf(am, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(s_)), bm);
+              y[e4] = glin ? s_ : e;
+            }
+            quad_transpose(y, q);
+            const float cn = __builtin_fmaf(y[1], cst[i][n], y[0] * y[2]);
+            float ca;
+            if constexpr (ACT == ACT_TANH) ca = __builtin_fmaf(__builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(GSC * cn)), 2.f, -1.f);
+            else if constexpr (ACT == ACT_SIGMOID) ca = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(GSC * cn));
+            else ca = cn;
+            hv = f2_rnd(y[3] * ca);
+            const float hh = __builtin_bit_cast(float, trunc_hi(hv));
+            hr = fa ? __builtin_fmaf(y[3], ca, -hh) : hv - hh;
+            cst[i][n] = cn;
+            if constexpr (TAPE) {
+              st4(f32x4{y[0], y[1], y[2], y[3]}, rt, tg);
+              st1(cn, rt, tc, 0);
+            }
+          } else {
+            float zd[4] = {zs[0], zs[1], zs[2], zs[3]};
+            quad_transpose(zd, q);
+            const f32x4 y = pg[n];
+            const float idot = y[0] * (1.f - y[0]) * zd[0], fdot = y[1] * (1.f - y[1]) * zd[1];
+            const float dg = ACT == ACT_TANH ? __builtin_fmaf(-y[2], y[2], 1.f) : ACT == ACT_SIGMOID ? y[2] * (1.f - y[2]) : 1.f;
+            const float gdot = dg * zd[2], odot = y[3] * (1.f - y[3]) * zd[3];
+            const float c = pc[n];
+            const float ca = act_f(ACT, c);
+            const float dc = ACT == ACT_TANH ? __builtin_fmaf(-ca, ca, 1.f) : ACT == ACT_SIGMOID ? ca * (1.f - ca) : 1.f;
+            const float yd = y[3] * dc;
+            float cdn, hd;
+            if (fa) {
+              if constexpr (ACT == ACT_LINEAR) {
+                cdn = f2_rnd(y[0] * gdot) + __builtin_fmaf(idot, y[2], __builtin_fmaf(fdot, cprev[i][n], y[1] * cst[i][n]));
+              } else {
+                cdn = __builtin_fmaf(y[0], gdot, f2_rnd(idot * y[2]) + (f2_rnd(y[1] * cst[i][n]) + f2_rnd(fdot * cprev[i][n])));
+              }
+              hd = f2_rnd(odot * ca) + f2_rnd(yd * cdn);
+            } else {
+              cdn = __builtin_fmaf(y[0], gdot, __builtin_fmaf(idot, y[2], __builtin_fmaf(y[1], cst[i][n], fdot * cprev[i][n])));
+              hd = __builtin_fmaf(odot, ca, yd * cdn);
+            }
+            cst[i][n] = cdn;
+            cprev[i][n] = c;
+            hv = hd;
+            hr = hv - __builtin_bit_cast(float, trunc_hi(hv));
+            st4(f32x4{zd[0], zd[1], zd[2], zd[3]}, rt, tg);
+            st1(cdn, rt, tc, 0);
+          }
+          // h (or hdot) of (row 16 m + 4 g + q, unit u) into the next step's planes (u < 96: tiles < 24) or
+          // the fp32 tail (tile 24, the last one of wave 7); the tile index is uniform
+          {
+            const int row = 16 * m + 4 * g + q;
+            if (t0 + n < 24) {
+              const uint32_t h1 = trunc_hi(hv);
+              const uint32_t m1 = trunc_hi(hr);
+              const uint32_t l1 = __builtin_bit_cast(uint32_t, hr - __builtin_bit_cast(float, m1));
+              lds_char* dp = hnext + (row * FS_HR + ub + 4 * n) * 2;
+              *reinterpret_cast<__attribute__((address_space(3))) uint16_t*>(dp) = (uint16_t)(h1 >> 16);
+              *reinterpret_cast<__attribute__((address_space(3))) uint16_t*>(dp + FS_HPL) = (uint16_t)(m1 >> 16);
+              *reinterpret_cast<__attribute__((address_space(3))) uint16_t*>(dp + 2 * FS_HPL) = (uint16_t)(l1 >> 16);
+            } else {
+              *reinterpret_cast<__attribute__((address_space(3))) float*>(hnext + 3 * FS_HPL + (row * 4 + j4) * 4) = hv;
+            }
+          }
+          st1(hv, rh, v1, 0);
+        }
+      }
+      xp.to_lds(xb + ((t + 1) & 1) * 32 * GX::LR, trash);
+      lds_barrier();
+    }
+  }
+}
+
+template <int ACT, int KX, bool TAPE, bool TAN, int SKEW>
+__global__ void __launch_bounds__(512, 1)
+lstmf_fwds2_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
+                   const float* __restrict__ U, const float* __restrict__ ptape, float* __restrict__ hs,
+                   float* __restrict__ tape, int B, int Tn) {
+  static_assert(FGeo<KX>::KS <= 12, "split forward: K <= 48");
+  extern __shared__ __attribute__((aligned(16))) float fsm[];
+  constexpr bool PRIO = SKEW & 1, FLIP = SKEW & 2;
+  const int v = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (v == 0) fwds2_run<ACT, KX, TAPE, TAN, 4, false, FLIP>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
+  else if (!PRIO || v < 4) fwds2_run<ACT, KX, TAPE, TAN, 3, false, FLIP>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
+  else fwds2_run<ACT, KX, TAPE, TAN, 3, true, FLIP>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
+}
+
+// ------------------------------------------------------------------------------------------
 // BPTT with the recurrent product on the bf16 matrix pipe: lstmf_bwds_kernel
 // ------------------------------------------------------------------------------------------
 // lstmf_bwdp_kernel's step is bound by dh_rec = dz_{t+1} U^T on the exact fp32 MFMA (400 16x16x4
@@ -1468,19 +1766,41 @@ template <int KX>
 constexpr size_t fwds_smem() {
   return (size_t)(2 * 32 * FGeo<KX>::LR) * 4 + 2 * FS_HB + 16;
 }
-// forward: 1 exact, 2 the split-recurrent forward for the K <= 36 layers (lstmf_fwds_kernel)
+static_assert(fwds2_smem<32>() <= F_LDS_MAX, "two-wave split forward LDS");
+// forward: 1 exact, 2 the split-recurrent forward for the K <= 36 layers (lstmf_fwds_kernel), 3 the split
+// forward on two waves per SIMD where it is instantiated (lstmf_fwds2_kernel, K = 32) and 2 elsewhere
 static std::atomic<int>& fwdf_impl() {
-  static std::atomic<int> v{fp32_exact() ? 1 : 2};
+  static std::atomic<int> v{fp32_exact() ? 1 : 3};
   return v;
 }
 static int fwdf_version() { return fwdf_impl().load(std::memory_order_relaxed); }
+template <int ACT, int KX, bool TAPE, bool TAN, int SKEW>
+void fwds2_launch(const float* x, const float* W, const float* b, const float* U, const float* pt, float* hs, float* tp,
+                  int B, int Tn, hipStream_t s) {
+  const int nrb = (B + 31) / 32, cus = device_cu_count();
+  auto k = lstmf_fwds2_kernel<ACT, KX, TAPE, TAN, SKEW>;
+  allow_lds(reinterpret_cast<const void*>(k));
+  hipLaunchKernelGGL(k, dim3(nrb < cus ? nrb : cus), dim3(512), fwds2_smem<KX>(), s, x, W, b, U, pt, hs, tp, B, Tn);
+}
 template <int ACT, int KX, bool TAPE, bool TAN>
 void fwdf_launch(const float* x, const float* W, const float* b, const float* U, const float* pt, float* hs, float* tp,
                  int B, int Tn, hipStream_t s) {
   const int nrb = (B + 31) / 32, cus = device_cu_count();
+  if constexpr (KX == 32) {
+    const int ver = fwdf_version();
+    if (ver == 3) return fwds2_launch<ACT, KX, TAPE, TAN, HFREP_FWDS2_SKEW>(x, W, b, U, pt, hs, tp, B, Tn, s);
+#ifdef HFREP_FWDS2_AB  // A/B builds only: impl 30 + SKEW selects a phase-skew variant (tanh)
+    if constexpr (ACT == ACT_TANH) {
+      if (ver == 30) return fwds2_launch<ACT, KX, TAPE, TAN, 0>(x, W, b, U, pt, hs, tp, B, Tn, s);
+      if (ver == 31) return fwds2_launch<ACT, KX, TAPE, TAN, 1>(x, W, b, U, pt, hs, tp, B, Tn, s);
+      if (ver == 32) return fwds2_launch<ACT, KX, TAPE, TAN, 2>(x, W, b, U, pt, hs, tp, B, Tn, s);
+      if (ver == 33) return fwds2_launch<ACT, KX, TAPE, TAN, 3>(x, W, b, U, pt, hs, tp, B, Tn, s);
+    }
+#endif
+  }
   // (K = 35 / 36 tangent forwards: the split kernel spills there -- registers; they stay exact)
   if constexpr (FGeo<KX>::KS <= 8 || (FGeo<KX>::KS <= 12 && !TAN)) {
-    if (fwdf_version() == 2) {
+    if (fwdf_version() >= 2) {
       auto k = lstmf_fwds_kernel<ACT, KX, TAPE, TAN>;
       allow_lds(reinterpret_cast<const void*>(k));
       hipLaunchKernelGGL(k, dim3(nrb < cus ? nrb : cus), dim3(256), fwds_smem<KX>(), s, x, W, b, U, pt, hs, tp, B, Tn);

@@ -38,8 +38,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=1, help="timed repeats per op (one JSON line each)")
     ap.add_argument("--only", default="fwd,tfwd,bwd,tbwd,bwd_dx,tbwd_dx,dgrad")
     ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float32"])
+    ap.add_argument("--fwd-impl", type=int, default=0, help="fp32: set_lstmf_fwd_impl value (0: the library default)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.fwd_impl:
+        from hfrep.ops import _native
+
+        _native.native().set_lstmf_fwd_impl(a.fwd_impl)
     B, T, K, H = a.batch, a.T, a.K, 100
     g = torch.Generator(device=dev).manual_seed(0)
     dt = getattr(torch, a.dtype)
@@ -71,7 +76,7 @@ def main():
     for name in a.only.split(","):
         for _ in range(a.repeats):
             ms = timeit(ops[name], a.iters)
-            print(json.dumps({"op": name, "dtype": a.dtype, "B": B, "T": T, "K": K, "ms": round(ms, 4),
+            print(json.dumps({"op": name, "dtype": a.dtype, "B": B, "T": T, "K": K, "act": a.act, "fwd_impl": a.fwd_impl, "ms": round(ms, 4),
                               "us_per_step": round(ms * 1e3 / T, 2)}), flush=True)
 
 
