@@ -308,6 +308,7 @@ std::tuple<Tensor, Tensor> lstm_tbwd(optional<Tensor> dH, Tensor dHd, Tensor gat
 bool lstmf_supported(int64_t H, int64_t K, int64_t act) { return hfrep::lstmf_supported((int)H, (int)K, (int)act); }
 bool narrowf_supported(int64_t K, int64_t N) { return hfrep::narrowf_supported((int)K, (int)N); }
 int64_t set_lstmf_fwd_impl(int64_t v) { return hfrep::set_lstmf_fwd_impl((int)v); }
+int64_t set_lstmf_fwd100_impl(int64_t v) { return hfrep::set_lstmf_fwd100_impl((int)v); }
 int64_t set_lstmf_bwd_impl(int64_t v) { return hfrep::set_lstmf_bwd_impl((int)v); }
 
 std::tuple<Tensor, Tensor> lstmf_fwd(Tensor x, Tensor W, optional<Tensor> b, Tensor U, int64_t act, bool save) {
@@ -1092,6 +1093,7 @@ TORCH_LIBRARY(hfrep, m) {
   m.def("lstmf_supported(int H, int K, int act) -> bool", &lstmf_supported);  // no tensor inputs: catch-all kernel
   m.def("narrowf_supported(int K, int N) -> bool", &narrowf_supported);
   m.def("set_lstmf_fwd_impl(int v) -> int", &set_lstmf_fwd_impl);
+  m.def("set_lstmf_fwd100_impl(int v) -> int", &set_lstmf_fwd100_impl);
   m.def("set_lstmf_bwd_impl(int v) -> int", &set_lstmf_bwd_impl);
   m.def("lstmf_fwd(Tensor x, Tensor W, Tensor? b, Tensor U, int act, bool save) -> (Tensor, Tensor)");
   m.def("linear_head_cs(Tensor x, Tensor W, Tensor? b, int split, float wa, float wb, Tensor(a!) gW, Tensor(b!)? gb) -> Tensor");

@@ -72,6 +72,7 @@ bool launch_lstmf_tbwd(const float* dH, const float* dHd, const float* tape, con
 // 3 = the same on eight waves, two per SIMD, where instantiated (K = 32; bitwise equal to 2, which the other
 // K <= 36 take; default); returns the previous setting
 int set_lstmf_fwd_impl(int v);  // 1: exact-fp32 forward everywhere, 2 / 3: the split-recurrent one for K <= 36
+int set_lstmf_fwd100_impl(int v);  // K = 100 forward, whatever the switch above: 1 four waves (lstmf_fwd_kernel), 2 eight waves (lstmf_fwd2_kernel; default, same bits)
 int set_lstmf_bwd_impl(int v);  // 2: the exact-fp32 BPTT kernel, 3: the split-recurrent one
 
 // ---- lstmf_grad.hip (fp32 LSTM gradient GEMMs; shared device helpers: lstmf_dev.h) ----

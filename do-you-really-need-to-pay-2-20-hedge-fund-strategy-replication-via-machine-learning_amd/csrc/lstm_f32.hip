@@ -26,6 +26,13 @@
 //  * outputs in the row-major layouts of the v1 contract (h (B,T,H), gate activations (B,T,4H),
 //    cells (B,T,H); the tangent's hdot, zdot, cdot), so the v1 reverse kernels consume them.
 //
+// At K = 100 (the second layer of both models) the forward runs on eight waves, two per SIMD, by default:
+// lstmf_fwd2_kernel regroups the 25 real tiles by columns (4 + 7 x 3, no padding tiles), keeps U^T in registers and
+// most of W^T in LDS, and runs one wave's gate math under its SIMD partner's MFMA chain; its outputs are bitwise
+// lstmf_fwd_kernel's (set_lstmf_fwd100_impl: 1 four waves, 2 eight waves; profiles/fwd100_two_wave/README.md).
+// lstmf_fwd_kernel stays as that reference, for K = 32 / 35 / 36 under forward impl 1 and for the K = 35 / 36
+// tangent forwards.
+//
 // TAN = true is the tangent forward at a saved primal point (ops/reference.py lstm_seq_tfwd with
 // dzx = xd W folded in): zdot_t = xd_t W + hdot_{t-1} U, primal gates / cells read from the tape.
 //
@@ -1558,6 +1565,258 @@ lstmf_fwds2_kernel(const float* __restrict__ x, const float* __restrict__ W, con
 }
 
 // ------------------------------------------------------------------------------------------
+// The exact K = 100 forward on 8 waves, two per SIMD: lstmf_fwd2_kernel
+// ------------------------------------------------------------------------------------------
+// lstmf_fwd_kernel at K = 100 runs one wave per SIMD: per step and row half a chain of 350 exact MFMAs (7
+// tiles x 50 k-steps), then the gate math of the 7 tiles, so the matrix pipe idles through every gate phase,
+// and every SIMD pays for 7 tiles although only 25 of the 28 are real.  Here the 25 real tiles (tile gt =
+// units 4 gt .. 4 gt + 3 = tile gt % 7 of wave gt / 7 there) go to 8 waves, waves v and v + 4 sharing a SIMD,
+// so one wave's gate math issues under its partner's MFMA chain.  Ownership is by columns, as in
+// lstmf_fwds2_kernel: wave 0 tiles 0..3, wave v > 0 tiles 3 v + 1 .. 3 v + 3 (7 / 6 / 6 / 6 tiles per SIMD),
+// each tile count its own straight-line instantiation behind one branch on the wave index at kernel entry.
+// 256 registers per wave: U^T stays in registers (25 per tile); of W^T's 25 k-steps a 3-tile wave keeps the
+// first 13 and the 4-tile wave the first 5, the rest sit in LDS as one ds_read_b128 per tile and four k-steps.
+// x_t is staged by waves 4..7 (3-tile waves).  The per-tile arithmetic is lstmf_fwd_kernel's:
+// zero accumulator, the 25 x W k-steps, the 25 h U k-steps, then the bias; the cell math is written out with
+// fmaf / f2_rnd in the forms the compiler gave that kernel (scripts/isa_fp_forms.py), so hs, hds and both
+// tapes are bitwise its outputs; the tape slots are its slots, those of its three padding tiles stay untouched.
+constexpr int F2_NWR3 = 13, F2_NWR4 = 5;  // W^T k-steps in registers: 3-tile / 4-tile waves
+constexpr int F2_G3 = (25 - F2_NWR3) / 4, F2_G4 = (25 - F2_NWR4) / 4;  // 1 KiB groups of 4 k-steps in LDS per tile
+static_assert(F2_NWR3 + 4 * F2_G3 == 25 && F2_NWR4 + 4 * F2_G4 == 25, "W^T k-steps in LDS come in fours");
+// first LDS group of tile gt: tiles 0..3 (wave 0) take F2_G4 groups each, the others F2_G3
+__device__ __forceinline__ constexpr int f2_woff(int gt) { return gt < 4 ? F2_G4 * gt : F2_G3 * gt + (F2_G4 - F2_G3) * 4; }
+constexpr size_t fwd2_smem() {
+  return (size_t)(2 * 32 * (FGeo<100>::LR + FGeo<FH>::LR) + 4) * 4 + (size_t)(F2_G3 * 25 + (F2_G4 - F2_G3) * 4) * 1024;
+}
+
+// one wave: tiles t0 .. t0 + NT - 1
+template <int ACT, bool TAPE, bool TAN, int NT>
+__device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const float* __restrict__ W,
+                                         const float* __restrict__ bias, const float* __restrict__ U,
+                                         const float* __restrict__ ptape, float* __restrict__ hs,
+                                         float* __restrict__ tape, int B, int Tn, float* fsm, int v) {
+  constexpr int KX = 100;
+  using GX = FGeo<KX>;
+  using GH = FGeo<FH>;
+  constexpr bool BIG = NT == 4;
+  constexpr int NWR = BIG ? F2_NWR4 : F2_NWR3, NG = BIG ? F2_G4 : F2_G3;
+  static_assert(GX::KS == 25 && GH::KS == 25 && (NT == 3 || NT == 4), "tile plan of the K = 100 layer");
+  float* xb = fsm;                         // [2][32 * LRX]
+  float* hb = xb + 2 * 32 * GX::LR;        // [2][32 * LRH]
+  float* trash = hb + 2 * 32 * GH::LR;     // [4] out-of-range x writes
+  f32x4* wl = (f32x4*)(trash + 4);         // [f2_woff(tile) + group][64 lanes]: W^T k-steps NWR + 4 group ..
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int q = lane & 3, g = lane >> 4, j4 = (lane & 15) >> 2;
+  const int t0 = v ? 3 * v + 1 : 0;  // first tile of this wave (uniform)
+  const int nrb = (B + 31) / 32;
+
+  for (int i = tid; i < 2 * 32 * (GX::LR + GH::LR); i += 512) fsm[i] = 0.f;
+
+  constexpr float GSC = ACT == ACT_TANH ? -2.f * kLog2e : ACT == ACT_SIGMOID ? -kLog2e : 1.f;
+  const float sc = TAN ? 1.f : (q == 2 ? GSC : -kLog2e);
+  float uf[GH::KS][NT], wf[NWR][NT], bq[NT];
+  int tsl[NT];  // tape slot of tile n, row half 0: the 4-wave kernel's (w, n) = (gt / 7, gt % 7) (bytes, uniform)
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const int gt = t0 + n;
+    const int cl = q * FH + 4 * gt + j4;  // < 400: every tile is real
+    tsl[n] = ftape_lane(gt / FNT, 0) + ((gt % FNT) * FT_SLOT) * 4;
+#pragma unroll
+    for (int ks = 0; ks < GH::KS; ++ks) {
+      uf[ks][n] = U[(4 * ks + g) * FG + cl] * sc;
+      // (no AGPR pin: a kernel that names AGPRs gets its 256 registers as 128 V + 128 A and spills)
+      asm volatile("" : "+v"(uf[ks][n]));
+    }
+#pragma unroll
+    for (int ks = 0; ks < NWR; ++ks) {
+      wf[ks][n] = W[(4 * ks + g) * FG + cl] * sc;
+      asm volatile("" : "+v"(wf[ks][n]));
+    }
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi) {
+      f32x4 wv;
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) wv[s4] = W[(4 * (NWR + 4 * gi + s4) + g) * FG + cl] * sc;
+      wl[(f2_woff(gt) + gi) * 64 + lane] = wv;
+    }
+    const float bv = bias ? bias[cl] : 0.f;
+    bq[n] = !TAN ? f2_rnd(bv * sc) : 0.f;
+  }
+  const bool glin = !TAN && ACT == ACT_LINEAR && q == 2;
+  const float am = q == 2 ? 2.f : 1.f, bm = q == 2 ? -1.f : 0.f;  // (tanh)
+  // LDS element offsets: A-fragment reads (row l & 15, k-group g) and the h write of (row 4 g + q, unit 4 gt + j4)
+  const int ax = (lane & 15) * GX::LR + g * GX::KQ, ah = (lane & 15) * GH::LR + g * GH::KQ;
+  const int hw = (4 * g + q) * GH::LR + j4 * GH::KQ + t0;
+  const f32x4* wlw = wl + f2_woff(t0) * 64 + lane;  // tile n: + n * NG * 64
+  // x_t: the 256 threads of waves 4..7 load and stage it; waves 1..3 write the trash word, the 4-tile wave has no loader
+  FXPart<KX> xp;
+  const bool xld = v >= 4;
+  __syncthreads();  // (the zero fill above, before any wave stages x_0)
+
+  for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const int row0 = rb * 32;
+    const rsrc_t rx = ftile_rsrc(x, row0, B, Tn, KX);
+    const rsrc_t rh = ftile_rsrc(hs, row0, B, Tn, FH);
+    const rsrc_t rt = ftape_rsrc(TAPE ? tape : nullptr, rb, nrb, Tn);
+    const rsrc_t rp = ftape_rsrc(TAN ? ptape : nullptr, rb, nrb, Tn);
+    const int vp0 = ((4 * g + q) * Tn * FH + 4 * t0 + j4) * 4;  // (row 4 g + q, unit of tile 0) in (B,T,H); half m adds 16 rows
+    float cprev[TAN ? 2 : 1][NT];
+    if constexpr (TAN) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) cprev[m][n] = 0.f;
+    }
+    float cst[2][NT];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) cst[m][n] = 0.f;
+    if constexpr (!BIG) {
+      xp.set(Tn, tid & 255);
+      if (!xld) {
+#pragma unroll
+        for (int j = 0; j < FXPart<KX>::NJ; ++j) { xp.goff[j] = kOOB; xp.lpos[j] = -1; }
+      }
+      xp.load(rx, Tn, 0, true);
+    }
+    for (int i = tid; i < 32 * GH::LR; i += 512) hb[i] = 0.f;  // h_{-1} = 0
+    if constexpr (!BIG) xp.to_lds(xb, trash);
+    __syncthreads();
+    for (int t = 0; t < Tn; ++t) {
+      const float* xcur = xb + (t & 1) * 32 * GX::LR;
+      const float* hcur = hb + (t & 1) * 32 * GH::LR;
+      float* hnext = hb + ((t + 1) & 1) * 32 * GH::LR;
+      if constexpr (!BIG) xp.load(rx, Tn, t + 1, t + 1 < Tn);  // x_{t+1}: lands during this step's MFMAs
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        f32x4 pg[TAN ? NT : 1];
+        float pc[TAN ? NT : 1];
+        const int p1 = vp0 + (16 * m * Tn + t) * FH * 4;
+        const int tb = t * FT_STEP * 4 + ftape_slot(m, 0);  // (uniform)
+        if constexpr (TAN) {
+          // the primal gates and c_t of this lane's (row, unit): issued before this half's MFMAs
+#pragma unroll
+          for (int n = 0; n < NT; ++n) {
+            pg[n] = ld4(rp, lane * 16 + (tb + tsl[n]));
+            pc[n] = ld1(rp, (256 + lane) * 4 + (tb + tsl[n]), 0);
+          }
+        }
+        f32x4 acc[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // ---- z = x_t W: k-steps < NWR from registers, then one b128 group per tile and four k-steps ----
+        f32x4 w4[NT];
+#pragma unroll
+        for (int j = 0; j < GX::NJ; ++j) {
+          const f32x4 a4 = *reinterpret_cast<const f32x4*>(xcur + ax + 16 * m * GX::LR + 4 * j);
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            const int ks = 4 * j + s;
+            if (ks >= GX::KS) break;
+            if (ks >= NWR && (ks - NWR) % 4 == 0) {
+#pragma unroll
+              for (int n = 0; n < NT; ++n) w4[n] = wlw[(n * NG + (ks - NWR) / 4) * 64];
+            }
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+              const float bw = ks < NWR ? wf[ks < NWR ? ks : 0][n] : w4[n][(ks >= NWR ? ks - NWR : 0) & 3];
+              acc[n] = mma4(a4[s], bw, acc[n]);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);  // bound the live range of hoisted fragment reads
+        }
+        // ---- + h_{t-1} U ----
+#pragma unroll
+        for (int j = 0; j < GH::NJ; ++j) {
+          const f32x4 a4 = *reinterpret_cast<const f32x4*>(hcur + ah + 16 * m * GH::LR + 4 * j);
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            const int ks = 4 * j + s;
+            if (ks >= GH::KS) break;
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[n] = mma4(a4[s], uf[ks][n], acc[n]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        // ---- gate math, cell update, stores (row 16 m + 4 g + q, unit 4 gt + j4 after the transpose) ----
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          // Every product-sum is written out, fused (fmaf) or rounded (f2_rnd), as the compiler contracted it
+          // in lstmf_fwd_kernel<ACT, 100>: one form per value everywhere, except the tangent's cdot in row
+          // half 0 of that kernel's tile 4 of every wave (odd, uniform)
+          const int v1 = p1 + 16 * n;
+          const int tg = lane * 16 + (tb + tsl[n]), tc = (256 + lane) * 4 + (tb + tsl[n]);
+          const f32x4 zs = acc[n];
+          float hv;
+          if constexpr (!TAN) {
+            float y[4];
+#pragma unroll
+            for (int e4 = 0; e4 < 4; ++e4) {
+              const float s_ = zs[e4] + bq[n];
+              const float r_ = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(s_));
+              float e = r_;
+              if constexpr (ACT == ACT_TANH) e = __builtin_fmaf(am, r_, bm);
+              y[e4] = glin ? s_ : e;
+            }
+            quad_transpose(y, q);  // y = (i, f, g, o) of (row, unit)
+            const float cn = __builtin_fmaf(y[1], cst[m][n], y[0] * y[2]);
+            float ca;
+            if constexpr (ACT == ACT_TANH) ca = __builtin_fmaf(__builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(GSC * cn)), 2.f, -1.f);
+            else if constexpr (ACT == ACT_SIGMOID) ca = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(GSC * cn));
+            else ca = cn;
+            hv = y[3] * ca;
+            cst[m][n] = cn;
+            if constexpr (TAPE) {
+              st4(f32x4{y[0], y[1], y[2], y[3]}, rt, tg);
+              st1(cn, rt, tc, 0);
+            }
+          } else {
+            float zd[4] = {zs[0], zs[1], zs[2], zs[3]};
+            quad_transpose(zd, q);  // zdot of (row, unit) for all four gates
+            const f32x4 y = pg[n];
+            const float idot = y[0] * (1.f - y[0]) * zd[0], fdot = y[1] * (1.f - y[1]) * zd[1];
+            const float dg = ACT == ACT_TANH ? __builtin_fmaf(-y[2], y[2], 1.f) : ACT == ACT_SIGMOID ? y[2] * (1.f - y[2]) : 1.f;
+            const float gdot = dg * zd[2], odot = y[3] * (1.f - y[3]) * zd[3];
+            const float c = pc[n];
+            const float ca = act_f(ACT, c);
+            const float dc = ACT == ACT_TANH ? __builtin_fmaf(-ca, ca, 1.f) : ACT == ACT_SIGMOID ? ca * (1.f - ca) : 1.f;
+            const float yd = y[3] * dc;
+            const float fc = __builtin_fmaf(fdot, cprev[m][n], y[1] * cst[m][n]);
+            float cdn = __builtin_fmaf(y[0], gdot, __builtin_fmaf(idot, y[2], fc));
+            if (m == 0 && (t0 + n) % FNT == 4) {  // (uniform)
+              if constexpr (ACT == ACT_LINEAR) cdn = f2_rnd(y[0] * gdot) + (f2_rnd(idot * y[2]) + (f2_rnd(fdot * cprev[m][n]) + f2_rnd(y[1] * cst[m][n])));
+              else cdn = __builtin_fmaf(y[0], gdot, f2_rnd(idot * y[2]) + fc);
+            }
+            hv = __builtin_fmaf(odot, ca, yd * cdn);
+            cst[m][n] = cdn;
+            cprev[m][n] = c;
+            st4(f32x4{zd[0], zd[1], zd[2], zd[3]}, rt, tg);
+            st1(cdn, rt, tc, 0);
+          }
+          hnext[hw + 16 * m * GH::LR + n] = hv;  // K-permuted: unit u at (u & 3) * KQ + (u >> 2)
+          st1(hv, rh, v1, 0);
+        }
+      }
+      if constexpr (!BIG) xp.to_lds(xb + ((t + 1) & 1) * 32 * GX::LR, trash);
+      lds_barrier();
+    }
+  }
+}
+
+template <int ACT, int KX, bool TAPE, bool TAN>
+__global__ void __launch_bounds__(512, 1)
+lstmf_fwd2_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
+                  const float* __restrict__ U, const float* __restrict__ ptape, float* __restrict__ hs,
+                  float* __restrict__ tape, int B, int Tn) {
+  static_assert(KX == 100, "the eight-wave exact forward is the K = 100 layer's");
+  extern __shared__ __attribute__((aligned(16))) float fsm[];
+  const int v = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (v == 0) fwd2_run<ACT, TAPE, TAN, 4>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
+  else fwd2_run<ACT, TAPE, TAN, 3>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
+}
+
+// ------------------------------------------------------------------------------------------
 // BPTT with the recurrent product on the bf16 matrix pipe: lstmf_bwds_kernel
 // ------------------------------------------------------------------------------------------
 // lstmf_bwdp_kernel's step is bound by dh_rec = dz_{t+1} U^T on the exact fp32 MFMA (400 16x16x4
@@ -1767,6 +2026,7 @@ constexpr size_t fwds_smem() {
   return (size_t)(2 * 32 * FGeo<KX>::LR) * 4 + 2 * FS_HB + 16;
 }
 static_assert(fwds2_smem<32>() <= F_LDS_MAX, "two-wave split forward LDS");
+static_assert(fwd2_smem() <= F_LDS_MAX, "eight-wave exact forward LDS");
 // forward: 1 exact, 2 the split-recurrent forward for the K <= 36 layers (lstmf_fwds_kernel), 3 the split
 // forward on two waves per SIMD where it is instantiated (lstmf_fwds2_kernel, K = 32) and 2 elsewhere
 static std::atomic<int>& fwdf_impl() {
@@ -1774,6 +2034,20 @@ static std::atomic<int>& fwdf_impl() {
   return v;
 }
 static int fwdf_version() { return fwdf_impl().load(std::memory_order_relaxed); }
+// the K = 100 forward, under every value of the switch above: 1 the four-wave lstmf_fwd_kernel, 2 the exact
+// forward on two waves per SIMD (lstmf_fwd2_kernel; same bits)
+static std::atomic<int>& fwdf100_impl() {
+  static std::atomic<int> v{2};
+  return v;
+}
+template <int ACT, int KX, bool TAPE, bool TAN>
+void fwd2_launch(const float* x, const float* W, const float* b, const float* U, const float* pt, float* hs, float* tp,
+                 int B, int Tn, hipStream_t s) {
+  const int nrb = (B + 31) / 32, cus = device_cu_count();
+  auto k = lstmf_fwd2_kernel<ACT, KX, TAPE, TAN>;
+  allow_lds(reinterpret_cast<const void*>(k));
+  hipLaunchKernelGGL(k, dim3(nrb < cus ? nrb : cus), dim3(512), fwd2_smem(), s, x, W, b, U, pt, hs, tp, B, Tn);
+}
 template <int ACT, int KX, bool TAPE, bool TAN, int SKEW>
 void fwds2_launch(const float* x, const float* W, const float* b, const float* U, const float* pt, float* hs, float* tp,
                   int B, int Tn, hipStream_t s) {
@@ -1786,6 +2060,10 @@ template <int ACT, int KX, bool TAPE, bool TAN>
 void fwdf_launch(const float* x, const float* W, const float* b, const float* U, const float* pt, float* hs, float* tp,
                  int B, int Tn, hipStream_t s) {
   const int nrb = (B + 31) / 32, cus = device_cu_count();
+  if constexpr (KX == 100) {
+    if (fwdf100_impl().load(std::memory_order_relaxed) == 2)
+      return fwd2_launch<ACT, KX, TAPE, TAN>(x, W, b, U, pt, hs, tp, B, Tn, s);
+  }
   if constexpr (KX == 32) {
     const int ver = fwdf_version();
     if (ver == 3) return fwds2_launch<ACT, KX, TAPE, TAN, HFREP_FWDS2_SKEW>(x, W, b, U, pt, hs, tp, B, Tn, s);
@@ -1834,6 +2112,7 @@ bool fwdf_k(int K, int act, const float* x, const float* W, const float* b, cons
 }  // namespace
 
 int set_lstmf_fwd_impl(int v) { return fwdf_impl().exchange(v); }
+int set_lstmf_fwd100_impl(int v) { return fwdf100_impl().exchange(v); }
 
 bool lstmf_supported(int H, int K, int act) {
   return H == FH && (K == 32 || K == 35 || K == 36 || K == 100) && (act == ACT_LINEAR || act == ACT_SIGMOID || act == ACT_TANH);

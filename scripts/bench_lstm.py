@@ -39,12 +39,18 @@ def main():
     ap.add_argument("--only", default="fwd,tfwd,bwd,tbwd,bwd_dx,tbwd_dx,dgrad")
     ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float32"])
     ap.add_argument("--fwd-impl", type=int, default=0, help="fp32: set_lstmf_fwd_impl value (0: the library default)")
+    ap.add_argument("--fwd100-impl", type=int, default=0,
+                    help="fp32, K = 100: set_lstmf_fwd100_impl value (1 four waves, 2 eight waves; 0: the library default)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.fwd_impl:
         from hfrep.ops import _native
 
         _native.native().set_lstmf_fwd_impl(a.fwd_impl)
+    if a.fwd100_impl:
+        from hfrep.ops import _native
+
+        _native.native().set_lstmf_fwd100_impl(a.fwd100_impl)
     B, T, K, H = a.batch, a.T, a.K, 100
     g = torch.Generator(device=dev).manual_seed(0)
     dt = getattr(torch, a.dtype)
@@ -76,7 +82,7 @@ def main():
     for name in a.only.split(","):
         for _ in range(a.repeats):
             ms = timeit(ops[name], a.iters)
-            print(json.dumps({"op": name, "dtype": a.dtype, "B": B, "T": T, "K": K, "act": a.act, "fwd_impl": a.fwd_impl, "ms": round(ms, 4),
+            print(json.dumps({"op": name, "dtype": a.dtype, "B": B, "T": T, "K": K, "act": a.act, "fwd_impl": a.fwd_impl, "fwd100_impl": a.fwd100_impl, "ms": round(ms, 4),
                               "us_per_step": round(ms * 1e3 / T, 2)}), flush=True)
 
 
