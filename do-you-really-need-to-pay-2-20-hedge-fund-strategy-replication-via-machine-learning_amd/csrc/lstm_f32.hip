@@ -27,7 +27,8 @@
 //    cells (B,T,H); the tangent's hdot, zdot, cdot), so the v1 reverse kernels consume them.
 //
 // At K = 100 (the second layer of both models) the forward runs on eight waves, two per SIMD, by default:
-// lstmf_fwd2_kernel regroups the 25 real tiles by columns (4 + 7 x 3, no padding tiles), keeps U^T in registers and
+// lstmf_fwd2_kernel regroups the 25 real tiles (8 x 3, tile 24 split by row half between waves 0 and 1, no
+// padding tiles: 13 / 13 / 12 / 12 tile-halves per SIMD), keeps U^T in registers and
 // most of W^T in LDS, and runs one wave's gate math under its SIMD partner's MFMA chain; its outputs are bitwise
 // lstmf_fwd_kernel's (set_lstmf_fwd100_impl: 1 four waves, 2 eight waves; profiles/fwd100_two_wave/README.md).
 // lstmf_fwd_kernel stays as that reference, for K = 32 / 35 / 36 under forward impl 1 and for the K = 35 / 36
@@ -1571,26 +1572,37 @@ lstmf_fwds2_kernel(const float* __restrict__ x, const float* __restrict__ W, con
 // tiles x 50 k-steps), then the gate math of the 7 tiles, so the matrix pipe idles through every gate phase,
 // and every SIMD pays for 7 tiles although only 25 of the 28 are real.  Here the 25 real tiles (tile gt =
 // units 4 gt .. 4 gt + 3 = tile gt % 7 of wave gt / 7 there) go to 8 waves, waves v and v + 4 sharing a SIMD,
-// so one wave's gate math issues under its partner's MFMA chain.  Ownership is by columns, as in
-// lstmf_fwds2_kernel: wave 0 tiles 0..3, wave v > 0 tiles 3 v + 1 .. 3 v + 3 (7 / 6 / 6 / 6 tiles per SIMD),
-// each tile count its own straight-line instantiation behind one branch on the wave index at kernel entry.
-// 256 registers per wave: U^T stays in registers (25 per tile); of W^T's 25 k-steps a 3-tile wave keeps the
-// first 13 and the 4-tile wave the first 5, the rest sit in LDS as one ds_read_b128 per tile and four k-steps.
-// x_t is staged by waves 4..7 (3-tile waves).  The per-tile arithmetic is lstmf_fwd_kernel's:
-// zero accumulator, the 25 x W k-steps, the 25 h U k-steps, then the bias; the cell math is written out with
-// fmaf / f2_rnd in the forms the compiler gave that kernel (scripts/isa_fp_forms.py), so hs, hds and both
-// tapes are bitwise its outputs; the tape slots are its slots, those of its three padding tiles stay untouched.
-constexpr int F2_NWR3 = 13, F2_NWR4 = 5;  // W^T k-steps in registers: 3-tile / 4-tile waves
+// so one wave's gate math issues under its partner's MFMA chain.  Ownership is balanced across the SIMDs by row
+// half: wave v owns tiles 3 v .. 3 v + 2 for both row halves, and tile 24 is held by waves 0 and 1, wave 0
+// running it for row half 0 and wave 1 for row half 1: 7 / 7 / 6 x 6 tile-halves per wave, 13 / 13 / 12 / 12 per
+// SIMD (lstmf_fwds2_kernel's ownership by whole columns, 14 / 12 / 12 / 12, was 5-7 % slower per call here; at
+// K = 32 it stays, profiles/fwd_balanced/README.md).  Each of the three roles (3 tiles; 3 + tile 24 in half 0;
+// 3 + tile 24 in half 1) is its own straight-line instantiation behind one branch on the wave index at kernel
+// entry, the tile count of a row half a compile-time function of the role.  256 registers per wave: U^T stays
+// in registers (25 per tile); of W^T's 25 k-steps a 3-tile wave keeps the first 13 and waves 0 and 1 the first 5
+// (of all four tiles), the rest sit in LDS as one ds_read_b128 per tile and four k-steps.  x_t is staged by
+// waves 2, 3, 6, 7 (the SIMDs with 12 tile-halves).  The per-tile arithmetic is lstmf_fwd_kernel's: zero
+// accumulator, the 25 x W k-steps, the 25 h U k-steps, then the bias; the cell math is written out with fmaf /
+// f2_rnd in the forms the compiler gave that kernel (scripts/isa_fp_forms.py), so hs, hds and both tapes are
+// bitwise its outputs; the tape slots are its slots, those of its three padding tiles stay untouched.
+constexpr int F2_NWR3 = 13, F2_NWR4 = 5;  // W^T k-steps in registers: waves 2..7 / waves 0 and 1
 constexpr int F2_G3 = (25 - F2_NWR3) / 4, F2_G4 = (25 - F2_NWR4) / 4;  // 1 KiB groups of 4 k-steps in LDS per tile
 static_assert(F2_NWR3 + 4 * F2_G3 == 25 && F2_NWR4 + 4 * F2_G4 == 25, "W^T k-steps in LDS come in fours");
-// first LDS group of tile gt: tiles 0..3 (wave 0) take F2_G4 groups each, the others F2_G3
-__device__ __forceinline__ constexpr int f2_woff(int gt) { return gt < 4 ? F2_G4 * gt : F2_G3 * gt + (F2_G4 - F2_G3) * 4; }
+// tile n of a wave relative to its first tile t0: its own three, then tile 24 (roles 1 and 2: waves 0 and 1,
+// t0 = 0 and 3)
+template <int ROLE>
+__device__ __forceinline__ constexpr int f2_rel(int n) { return n < 3 ? n : 24 - 3 * (ROLE - 1); }
+// first LDS group of tile gt: tiles 0..5 and 24 (waves 0 and 1) take F2_G4 groups each and come first, tile 24
+// (one copy, read by both waves) behind tile 5; the others take F2_G3
+__device__ __forceinline__ constexpr int f2_woff(int gt) {
+  return gt < 6 ? F2_G4 * gt : gt == 24 ? F2_G4 * 6 : F2_G4 * 7 + F2_G3 * (gt - 6);
+}
 constexpr size_t fwd2_smem() {
-  return (size_t)(2 * 32 * (FGeo<100>::LR + FGeo<FH>::LR) + 4) * 4 + (size_t)(F2_G3 * 25 + (F2_G4 - F2_G3) * 4) * 1024;
+  return (size_t)(2 * 32 * (FGeo<100>::LR + FGeo<FH>::LR) + 4) * 4 + (size_t)(F2_G4 * 7 + F2_G3 * 18) * 1024;
 }
 
-// one wave: tiles t0 .. t0 + NT - 1
-template <int ACT, bool TAPE, bool TAN, int NT>
+// one wave: tiles t0 .. t0 + 2 and, for ROLE 1 / 2, tile 24 in row half ROLE - 1
+template <int ACT, bool TAPE, bool TAN, int ROLE>
 __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const float* __restrict__ W,
                                          const float* __restrict__ bias, const float* __restrict__ U,
                                          const float* __restrict__ ptape, float* __restrict__ hs,
@@ -1598,16 +1610,17 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
   constexpr int KX = 100;
   using GX = FGeo<KX>;
   using GH = FGeo<FH>;
-  constexpr bool BIG = NT == 4;
+  constexpr bool BIG = ROLE != 0;
+  constexpr int NT = BIG ? 4 : 3;  // tiles held
   constexpr int NWR = BIG ? F2_NWR4 : F2_NWR3, NG = BIG ? F2_G4 : F2_G3;
-  static_assert(GX::KS == 25 && GH::KS == 25 && (NT == 3 || NT == 4), "tile plan of the K = 100 layer");
+  static_assert(GX::KS == 25 && GH::KS == 25 && ROLE >= 0 && ROLE <= 2, "tile plan of the K = 100 layer");
   float* xb = fsm;                         // [2][32 * LRX]
   float* hb = xb + 2 * 32 * GX::LR;        // [2][32 * LRH]
   float* trash = hb + 2 * 32 * GH::LR;     // [4] out-of-range x writes
   f32x4* wl = (f32x4*)(trash + 4);         // [f2_woff(tile) + group][64 lanes]: W^T k-steps NWR + 4 group ..
   const int tid = threadIdx.x, lane = tid & 63;
   const int q = lane & 3, g = lane >> 4, j4 = (lane & 15) >> 2;
-  const int t0 = v ? 3 * v + 1 : 0;  // first tile of this wave (uniform)
+  const int t0 = BIG ? 3 * (ROLE - 1) : 3 * v;  // first tile of this wave (uniform; a constant for waves 0 and 1)
   const int nrb = (B + 31) / 32;
 
   for (int i = tid; i < 2 * 32 * (GX::LR + GH::LR); i += 512) fsm[i] = 0.f;
@@ -1618,7 +1631,7 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
   int tsl[NT];  // tape slot of tile n, row half 0: the 4-wave kernel's (w, n) = (gt / 7, gt % 7) (bytes, uniform)
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
-    const int gt = t0 + n;
+    const int gt = t0 + f2_rel<ROLE>(n);
     const int cl = q * FH + 4 * gt + j4;  // < 400: every tile is real
     tsl[n] = ftape_lane(gt / FNT, 0) + ((gt % FNT) * FT_SLOT) * 4;
 #pragma unroll
@@ -1637,7 +1650,7 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
       f32x4 wv;
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) wv[s4] = W[(4 * (NWR + 4 * gi + s4) + g) * FG + cl] * sc;
-      wl[(f2_woff(gt) + gi) * 64 + lane] = wv;
+      if (n < 3 || ROLE == 1) wl[(f2_woff(gt) + gi) * 64 + lane] = wv;  // (tile 24's one copy: wave 0 writes it)
     }
     const float bv = bias ? bias[cl] : 0.f;
     bq[n] = !TAN ? f2_rnd(bv * sc) : 0.f;
@@ -1647,10 +1660,14 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
   // LDS element offsets: A-fragment reads (row l & 15, k-group g) and the h write of (row 4 g + q, unit 4 gt + j4)
   const int ax = (lane & 15) * GX::LR + g * GX::KQ, ah = (lane & 15) * GH::LR + g * GH::KQ;
   const int hw = (4 * g + q) * GH::LR + j4 * GH::KQ + t0;
-  const f32x4* wlw = wl + f2_woff(t0) * 64 + lane;  // tile n: + n * NG * 64
-  // x_t: the 256 threads of waves 4..7 load and stage it; waves 1..3 write the trash word, the 4-tile wave has no loader
+  const f32x4* wlw = wl + f2_woff(t0) * 64 + lane;  // tile n: + wrel(n) * 64
+  constexpr int WR24 = BIG ? f2_woff(24) - f2_woff(3 * (ROLE - 1)) : 0;  // tile 24 from t0 (waves 0 and 1 only)
+  auto wrel = [](int n) constexpr { return n < 3 ? n * NG : WR24; };  // (n = 3 occurs in those two roles only)
+  // x_t: the 256 threads of waves 2, 3, 6, 7 load and stage it; waves 4 and 5 write the trash word, waves 0 and 1
+  // have no loader
   FXPart<KX> xp;
-  const bool xld = v >= 4;
+  const bool xld = (v & 2) != 0;
+  const int xtid = (((v >> 2) << 1) | (v & 1)) * 64 + lane;  // loaders: 0..255
   __syncthreads();  // (the zero fill above, before any wave stages x_0)
 
   for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
@@ -1667,13 +1684,13 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
 #pragma unroll
         for (int n = 0; n < NT; ++n) cprev[m][n] = 0.f;
     }
-    float cst[2][NT];
+    float cst[2][NT];  // (tile 24, n = 3: only the entries of row half ROLE - 1 are live)
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int n = 0; n < NT; ++n) cst[m][n] = 0.f;
     if constexpr (!BIG) {
-      xp.set(Tn, tid & 255);
+      xp.set(Tn, xtid);
       if (!xld) {
 #pragma unroll
         for (int j = 0; j < FXPart<KX>::NJ; ++j) { xp.goff[j] = kOOB; xp.lpos[j] = -1; }
@@ -1688,25 +1705,27 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
       const float* hcur = hb + (t & 1) * 32 * GH::LR;
       float* hnext = hb + ((t + 1) & 1) * 32 * GH::LR;
       if constexpr (!BIG) xp.load(rx, Tn, t + 1, t + 1 < Tn);  // x_{t+1}: lands during this step's MFMAs
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        f32x4 pg[TAN ? NT : 1];
-        float pc[TAN ? NT : 1];
+      // one row half: NH tiles, a compile-time function of the role (tile 24 in row half ROLE - 1 only)
+      auto half = [&](auto M_) {
+        constexpr int m = decltype(M_)::value;
+        constexpr int NH = (BIG && m == ROLE - 1) ? 4 : 3;
+        f32x4 pg[TAN ? NH : 1];
+        float pc[TAN ? NH : 1];
         const int p1 = vp0 + (16 * m * Tn + t) * FH * 4;
         const int tb = t * FT_STEP * 4 + ftape_slot(m, 0);  // (uniform)
         if constexpr (TAN) {
           // the primal gates and c_t of this lane's (row, unit): issued before this half's MFMAs
 #pragma unroll
-          for (int n = 0; n < NT; ++n) {
+          for (int n = 0; n < NH; ++n) {
             pg[n] = ld4(rp, lane * 16 + (tb + tsl[n]));
             pc[n] = ld1(rp, (256 + lane) * 4 + (tb + tsl[n]), 0);
           }
         }
-        f32x4 acc[NT];
+        f32x4 acc[NH];
 #pragma unroll
-        for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < NH; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
         // ---- z = x_t W: k-steps < NWR from registers, then one b128 group per tile and four k-steps ----
-        f32x4 w4[NT];
+        f32x4 w4[NH];
 #pragma unroll
         for (int j = 0; j < GX::NJ; ++j) {
           const f32x4 a4 = *reinterpret_cast<const f32x4*>(xcur + ax + 16 * m * GX::LR + 4 * j);
@@ -1716,10 +1735,10 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
             if (ks >= GX::KS) break;
             if (ks >= NWR && (ks - NWR) % 4 == 0) {
 #pragma unroll
-              for (int n = 0; n < NT; ++n) w4[n] = wlw[(n * NG + (ks - NWR) / 4) * 64];
+              for (int n = 0; n < NH; ++n) w4[n] = wlw[(wrel(n) + (ks - NWR) / 4) * 64];
             }
 #pragma unroll
-            for (int n = 0; n < NT; ++n) {
+            for (int n = 0; n < NH; ++n) {
               const float bw = ks < NWR ? wf[ks < NWR ? ks : 0][n] : w4[n][(ks >= NWR ? ks - NWR : 0) & 3];
               acc[n] = mma4(a4[s], bw, acc[n]);
             }
@@ -1735,17 +1754,17 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
             const int ks = 4 * j + s;
             if (ks >= GH::KS) break;
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[n] = mma4(a4[s], uf[ks][n], acc[n]);
+            for (int n = 0; n < NH; ++n) acc[n] = mma4(a4[s], uf[ks][n], acc[n]);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
         // ---- gate math, cell update, stores (row 16 m + 4 g + q, unit 4 gt + j4 after the transpose) ----
 #pragma unroll
-        for (int n = 0; n < NT; ++n) {
+        for (int n = 0; n < NH; ++n) {
           // Every product-sum is written out, fused (fmaf) or rounded (f2_rnd), as the compiler contracted it
           // in lstmf_fwd_kernel<ACT, 100>: one form per value everywhere, except the tangent's cdot in row
-          // half 0 of that kernel's tile 4 of every wave (odd, uniform)
-          const int v1 = p1 + 16 * n;
+          // half 0 of that kernel's tile 4 of every wave (global tiles 4, 11, 18; odd, uniform)
+          const int v1 = p1 + 16 * f2_rel<ROLE>(n);
           const int tg = lane * 16 + (tb + tsl[n]), tc = (256 + lane) * 4 + (tb + tsl[n]);
           const f32x4 zs = acc[n];
           float hv;
@@ -1784,7 +1803,7 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
             const float yd = y[3] * dc;
             const float fc = __builtin_fmaf(fdot, cprev[m][n], y[1] * cst[m][n]);
             float cdn = __builtin_fmaf(y[0], gdot, __builtin_fmaf(idot, y[2], fc));
-            if (m == 0 && (t0 + n) % FNT == 4) {  // (uniform)
+            if (m == 0 && (t0 + f2_rel<ROLE>(n)) % FNT == 4) {  // (uniform)
               if constexpr (ACT == ACT_LINEAR) cdn = f2_rnd(y[0] * gdot) + (f2_rnd(idot * y[2]) + (f2_rnd(fdot * cprev[m][n]) + f2_rnd(y[1] * cst[m][n])));
               else cdn = __builtin_fmaf(y[0], gdot, f2_rnd(idot * y[2]) + fc);
             }
@@ -1794,10 +1813,12 @@ __device__ __forceinline__ void fwd2_run(const float* __restrict__ x, const floa
             st4(f32x4{zd[0], zd[1], zd[2], zd[3]}, rt, tg);
             st1(cdn, rt, tc, 0);
           }
-          hnext[hw + 16 * m * GH::LR + n] = hv;  // K-permuted: unit u at (u & 3) * KQ + (u >> 2)
+          hnext[hw + 16 * m * GH::LR + f2_rel<ROLE>(n)] = hv;  // K-permuted: unit u at (u & 3) * KQ + (u >> 2)
           st1(hv, rh, v1, 0);
         }
-      }
+      };
+      half(I0{});
+      half(I1{});
       if constexpr (!BIG) xp.to_lds(xb + ((t + 1) & 1) * 32 * GX::LR, trash);
       lds_barrier();
     }
@@ -1812,8 +1833,9 @@ lstmf_fwd2_kernel(const float* __restrict__ x, const float* __restrict__ W, cons
   static_assert(KX == 100, "the eight-wave exact forward is the K = 100 layer's");
   extern __shared__ __attribute__((aligned(16))) float fsm[];
   const int v = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (v == 0) fwd2_run<ACT, TAPE, TAN, 4>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
-  else fwd2_run<ACT, TAPE, TAN, 3>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
+  if (v == 0) fwd2_run<ACT, TAPE, TAN, 1>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
+  else if (v == 1) fwd2_run<ACT, TAPE, TAN, 2>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
+  else fwd2_run<ACT, TAPE, TAN, 0>(x, W, bias, U, ptape, hs, tape, B, Tn, fsm, v);
 }
 
 // ------------------------------------------------------------------------------------------
