@@ -362,12 +362,16 @@ def cmd_replicate(a) -> int:
         latents = list(range(int(lo), int(hi or lo) + 1))
         daily, _ = load_daily_etf()
         t0 = time.perf_counter()
-        st = daily_factor_study(daily, latents=latents, seeds=[a.seed], device=dev, dtype=dt)
+        st = daily_factor_study(daily, latents=latents, seeds=[a.seed], device=dev, dtype=dt,
+                                oos_stride=a.oos_stride or 21)
         res["ae_sweep_daily"] = {"device": str(dev), "dtype": a.dtype, "seed": a.seed, "rows": int(len(daily)),
                                  "period": [str(daily.index[0].date()), str(daily.index[-1].date())],
                                  "elapsed_s": round(time.perf_counter() - t0, 3),
                                  "fit_s": round(float(st["fit_s"].iloc[0]), 3),
-                                 "metrics": st.set_index("latent").drop(columns=["seed", "fit_s"]).to_dict(orient="index")}
+                                 "eval_s": round(float(st["eval_s"].iloc[0]), 3),
+                                 "oos_stride": a.oos_stride or 21,
+                                 "metrics": st.set_index("latent").drop(columns=["seed", "fit_s", "eval_s"])
+                                 .to_dict(orient="index")}
     elif a.method == "ae-sweep":
         from .finance.experiment import generated_augmentation, latent_sweep
 
@@ -378,7 +382,7 @@ def cmd_replicate(a) -> int:
             xe, ye = generated_augmentation(np.load(a.augment, allow_pickle=False), c)
         t0 = time.perf_counter()
         sw = latent_sweep(c, latents=latents, window=a.window, x_extra=xe, y_extra=ye, verbose=True, device=dev,
-                          dtype=dt, seed=a.seed)
+                          dtype=dt, seed=a.seed, oos_stride=a.oos_stride or 1)
         res["ae_sweep"] = {"device": str(dev), "dtype": a.dtype, "seed": a.seed, "augmented": bool(a.augment),
                            "elapsed_s": round(time.perf_counter() - t0, 3),
                            "metrics": sw.metrics.to_dict(orient="index"),
@@ -444,6 +448,8 @@ def main(argv=None) -> int:
     r.add_argument("--freq", default="monthly", choices=["monthly", "daily"],
                    help="ae-sweep panel: the 337-month cleaned panel (reference) or the daily ETF excess-return "
                         "matrix (BASELINE config 2, data.cleaning.build_factor_etf_daily)")
+    r.add_argument("--oos-stride", type=int, default=None,
+                   help="ae-sweep: one expanding OOS window every N test rows (default: 21 for --freq daily, 1 monthly)")
     r.add_argument("--augment", default=None, help="ae-sweep: generated windows .npy (F=36) to add to training")
     r.add_argument("--window", type=int, default=24)
     r.add_argument("--latent", type=int, default=12)

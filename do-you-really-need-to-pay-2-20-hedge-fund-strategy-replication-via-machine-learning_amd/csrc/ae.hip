@@ -19,6 +19,7 @@
 // rounded to bf16 where the engine stores a bf16 tensor (inputs, Dense outputs, LeakyReLU outputs,
 // y - x, the MSE gradient, the reverse-pass adjoints), products are exact bf16 x bf16 products summed
 // in fp32 (the bf16 MFMA's arithmetic), and master weights, gradients and optimizer slots are fp32.
+#include "ae_dev.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -26,15 +27,10 @@ namespace hfrep {
 
 namespace {
 
-// (LDS: 5 activation tiles of 64 x 32 floats + 4 weight images of 32 x 32 = 56 KiB)
-constexpr int AE_MAXA = 32, AE_MAXK = 32, AE_MAXB = 64, AE_THREADS = 256;
+// (LDS: 5 activation tiles of 64 x 32 floats + 4 weight images of 32 x 32 = 56 KiB; AE_MAXA, AE_MAXK,
+// rnd<BF> and lrelu come from ae_dev.h)
+constexpr int AE_MAXB = 64, AE_THREADS = 256;
 
-template <bool BF>
-__device__ __forceinline__ float rnd(float v) {
-  if constexpr (BF) return bf2f(f2bf(v));
-  else return v;
-}
-__device__ __forceinline__ float lrelu(float x) { return x >= 0.f ? x : 0.2f * x; }
 __device__ __forceinline__ float lrelu_dy(float y) { return y >= 0.f ? 1.f : 0.2f; }
 
 // fixed-order block sum of one double per thread (tree over LDS): every thread gets the total

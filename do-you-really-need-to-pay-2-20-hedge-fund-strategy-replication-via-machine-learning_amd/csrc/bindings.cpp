@@ -861,6 +861,88 @@ std::tuple<Tensor, Tensor> ae_fit(at::TensorList Xt, at::TensorList Xv, at::Tens
   return {hist, nep};
 }
 
+// The refit MinMaxScaler and ss_tot of every window x[:ends[w]] (csrc/ae_eval.hip): x (A, n) fp64 (the panel
+// transposed: one contiguous row per data column), ends (W,) int32 in [1, n].  Returns scale_, min_ and
+// ss_tot, (W, A) fp64 each; refit = false gives the identity scaler (the panel is scaled already).
+std::tuple<Tensor, Tensor, Tensor> ae_window_table(Tensor x, Tensor ends, bool refit) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kDouble && x.is_contiguous() && x.dim() == 2,
+              "ae_window_table: x must be a contiguous (A, n) fp64 GPU tensor");
+  TORCH_CHECK(ends.device() == x.device() && ends.scalar_type() == at::kInt && ends.is_contiguous() && ends.dim() == 1,
+              "ae_window_table: ends must be a contiguous (W,) int32 tensor on x's device");
+  const int64_t A = x.size(0), n = x.size(1), W = ends.size(0);
+  TORCH_CHECK(A >= 1 && A <= 32 && n >= 1 && n < (int64_t)1 << 31 && W * A < (int64_t)1 << 31, "ae_window_table: sizes");
+  GUARD(x);
+  Tensor scale = out_empty({W, A}, x.options()), mn = out_empty({W, A}, x.options()), sstot = out_empty({W, A}, x.options());
+  hfrep::launch_ae_window_table(x.data_ptr<double>(), ends.data_ptr<int>(), scale.data_ptr<double>(), mn.data_ptr<double>(),
+                                sstot.data_ptr<double>(), (int)A, (int)n, (int)W, refit, cur_stream(x));
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "ae_window_table: launch failed: ", hipGetErrorString(err));
+  return {scale, mn, sstot};
+}
+
+// R^2 and RMSE of every (autoencoder, window) in ONE launch (csrc/ae_eval.hip, one wave each).  Per job: its
+// panel x (A, n) fp64, the window ends and table of ae_window_table, We (A, k) / Wd (k, A) fp32.  work (N, 2)
+// int32: the (job, window) pairs in launch order, every window of every job exactly once (only the pairs named
+// are written; the count is checked here).  Returns r2 and rmse, fp64, the jobs' windows concatenated.
+std::tuple<Tensor, Tensor> ae_recon_metrics(at::TensorList x, at::TensorList ends, at::TensorList scale, at::TensorList mn,
+                                            at::TensorList sstot, at::TensorList We, at::TensorList Wd, Tensor work,
+                                            bool bf16) {
+  const size_t nj = x.size();
+  TORCH_CHECK(nj >= 1, "ae_recon_metrics: at least one job");
+  for (at::TensorList l : {ends, scale, mn, sstot, We, Wd})
+    TORCH_CHECK(l.size() == nj, "ae_recon_metrics: every per-job list needs ", nj, " entries");
+  const auto dev = x[0].device();
+  TORCH_CHECK(x[0].is_cuda() && x[0].dim() == 2, "ae_recon_metrics: x (A, n) on the GPU");
+  const int64_t A = x[0].size(0);
+  TORCH_CHECK(work.device() == dev && work.scalar_type() == at::kInt && work.is_contiguous() && work.dim() == 2 &&
+                  work.size(1) == 2 && work.size(0) < (int64_t)1 << 31,
+              "ae_recon_metrics: work must be a contiguous (N, 2) int32 tensor on the jobs' device");
+  std::vector<hfrep::AeEvalJob> jobs(nj);
+  int64_t total = 0;
+  for (size_t i = 0; i < nj; ++i) {
+    for (const Tensor* t : {&x[i], &scale[i], &mn[i], &sstot[i]})
+      TORCH_CHECK(t->device() == dev && t->scalar_type() == at::kDouble && t->is_contiguous() && t->dim() == 2,
+                  "ae_recon_metrics: x and the window table must be contiguous 2-d fp64 tensors on one device");
+    CHECK_F32(We[i]); CHECK_F32(Wd[i]);
+    TORCH_CHECK(We[i].device() == dev && Wd[i].device() == dev, "ae_recon_metrics: weights on the jobs' device");
+    const Tensor& e = ends[i];
+    TORCH_CHECK(e.device() == dev && e.scalar_type() == at::kInt && e.is_contiguous() && e.dim() == 1,
+                "ae_recon_metrics: ends must be a contiguous (W,) int32 tensor");
+    const int64_t n = x[i].size(1), W = e.size(0), k = We[i].numel() / A;
+    TORCH_CHECK(x[i].size(0) == A && n >= 1 && n < (int64_t)1 << 31, "ae_recon_metrics: one input width A for every job");
+    for (const Tensor* t : {&scale[i], &mn[i], &sstot[i]})
+      TORCH_CHECK(t->size(0) == W && t->size(1) == A, "ae_recon_metrics: window table must be (W, A)");
+    TORCH_CHECK(We[i].numel() == A * k && Wd[i].numel() == A * k, "ae_recon_metrics: weight sizes");
+    TORCH_CHECK(hfrep::ae_fit_supported((int)A, (int)k, 1), "ae_recon_metrics: A, k <= 32");
+    hfrep::AeEvalJob& J = jobs[i];
+    J.X = x[i].data_ptr<double>();
+    J.ends = e.data_ptr<int>();
+    J.scale = scale[i].data_ptr<double>(); J.mn = mn[i].data_ptr<double>(); J.sstot = sstot[i].data_ptr<double>();
+    J.We = We[i].data_ptr<float>(); J.Wd = Wd[i].data_ptr<float>();
+    J.n = (int)n; J.W = (int)W; J.k = (int)k; J.pad_ = 0;
+    total += W;
+  }
+  TORCH_CHECK(work.size(0) == total, "ae_recon_metrics: work must name every (job, window) pair once: ", total,
+              " windows, ", work.size(0), " pairs");
+  GUARD(x[0]);
+  Tensor r2 = out_empty({total}, x[0].options()), rm = out_empty({total}, x[0].options());
+  int64_t off = 0;
+  for (size_t i = 0; i < nj; ++i) {
+    jobs[i].r2 = r2.data_ptr<double>() + off;
+    jobs[i].rmse = rm.data_ptr<double>() + off;
+    off += jobs[i].W;
+  }
+  const int64_t bytes = (int64_t)(nj * sizeof(hfrep::AeEvalJob));
+  Tensor host = at::empty({bytes}, at::TensorOptions().dtype(at::kByte));
+  std::memcpy(host.data_ptr(), jobs.data(), bytes);
+  Tensor dj = host.to(dev);
+  hfrep::launch_ae_recon_metrics(bf16, reinterpret_cast<const hfrep::AeEvalJob*>(dj.data_ptr()), (int)nj,
+                                 work.data_ptr<int>(), (int)work.size(0), (int)A, cur_stream(x[0]));
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "ae_recon_metrics: launch failed: ", hipGetErrorString(err));
+  return {r2, rm};
+}
+
 // ------------------------------------------------------------------------------------ optimizers
 // the device-resident scalars (iterations, Nadam momentum cache): one element, on the parameters' device
 #define CHECK_COUNTER(t, like, what) \
@@ -1133,6 +1215,9 @@ TORCH_LIBRARY(hfrep, m) {
   m.def("ae_fit(Tensor[] Xt, Tensor[] Xv, Tensor[] order, Tensor(a!)[] We, Tensor(b!)[] Wd, Tensor(c!)[] mWe, "
         "Tensor(d!)[] vWe, Tensor(e!)[] mWd, Tensor(f!)[] vWd, Tensor(g!)[] step, Tensor(h!)[] m_cache, int[] patience, "
         "float lr, float b1, float b2, float eps, int batch, bool bf16) -> (Tensor, Tensor)");
+  m.def("ae_window_table(Tensor x, Tensor ends, bool refit) -> (Tensor, Tensor, Tensor)");
+  m.def("ae_recon_metrics(Tensor[] x, Tensor[] ends, Tensor[] scale, Tensor[] mn, Tensor[] sstot, Tensor[] We, Tensor[] Wd, "
+        "Tensor work, bool bf16) -> (Tensor, Tensor)");
   m.def("rmsprop_(Tensor(a!) p, Tensor g, Tensor(b!) ms, float lr, float rho, float eps, float clip, float gscale) -> ()");
   m.def("adam_(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor step, float lr, float b1, float b2, float eps, float clip, float gscale) -> ()");
   m.def("nadam_(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor step, Tensor m_cache, float lr, float b1, float b2, float eps, float gscale) -> ()");
@@ -1191,6 +1276,8 @@ TORCH_LIBRARY_IMPL(hfrep, CUDA, m) {
   m.impl("philox_fill_", &philox_fill_);
   m.impl("sample_windows", &sample_windows);
   m.impl("ae_fit", &ae_fit);
+  m.impl("ae_window_table", &ae_window_table);
+  m.impl("ae_recon_metrics", &ae_recon_metrics);
   m.impl("rmsprop_", &rmsprop_);
   m.impl("adam_", &adam_);
   m.impl("nadam_", &nadam_);

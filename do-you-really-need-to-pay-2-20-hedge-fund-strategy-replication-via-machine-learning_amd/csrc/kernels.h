@@ -110,6 +110,27 @@ struct AeFitJob {
 void launch_ae_fit(bool bf16, const AeFitJob* jobs, int njobs, int batch, float lr, float b1, float b2, float eps, int A,
                    hipStream_t s);
 
+// ---- ae_eval.hip (factor autoencoder: the IS / OOS reconstruction metrics of a whole study) ----
+// Per window x[:ends[w]] of the panel X (A, n) fp64 (one row of X per column of the data) and per column:
+// the refit MinMaxScaler's scale_ and min_ (bitwise data/scaler.py) and ss_tot of the scaled window,
+// each (W, A) fp64.  refit = false: the identity scaler (scale_ 1, min_ 0).  One wave per (window, column).
+void launch_ae_window_table(const double* X, const int* ends, double* scale, double* mn, double* sstot, int A, int n,
+                            int W, bool refit, hipStream_t s);
+// one autoencoder's evaluation: its panel and window table, its weights We (A, k) / Wd (k, A), and the
+// per-window outputs r2 / rmse (W each)
+struct AeEvalJob {
+  const double* X;
+  const int* ends;
+  const double *scale, *mn, *sstot;
+  const float *We, *Wd;
+  double *r2, *rmse;
+  int n, W, k, pad_;
+};
+// `jobs`: device array of njobs records; `work`: device array of nwork (job, window) pairs, one wave each,
+// run in the order given (heaviest windows first).  A, k <= 32 (ae_fit_supported's limits).
+void launch_ae_recon_metrics(bool bf16, const AeEvalJob* jobs, int njobs, const int* work, int nwork, int A,
+                             hipStream_t s);
+
 // ---- gemm.hip ----
 // C[M,N] = act(A[M,K] . op(W) + bias);  op(W) = W (K,N) or W^T when w_trans (W stored (N,K)).
 // A and C share the activation dtype `dt`; W and bias are fp32 (converted while staging).

@@ -175,6 +175,94 @@ def fit_fused_many(jobs: list, batch_size: int, dtype, verbose: int = 0) -> list
 
 
 # ------------------------------------------------------------------------------------------
+# IS / OOS reconstruction metrics of many AEs on the device (csrc/ae_eval.hip)
+# ------------------------------------------------------------------------------------------
+def _metrics_device_ok(aes: list) -> bool:
+    """Whether ``AE.metrics_many`` can take the device path for these (trained) AEs; the panels'
+    finiteness is checked where they are uploaded."""
+    a0 = aes[0]
+    A = a0._x_train.shape[1]
+    if not (all(a.autoencoder is not None and a.device.type == "cuda" and a.device == a0.device
+                and a.dtype == a0.dtype and a._x_train.shape[1] == A for a in aes)
+            and a0.dtype in (torch.float32, torch.bfloat16)
+            and _native.use_native_for(torch.empty(0, device=a0.device))):
+        return False
+    return all(bool(_native.native().ae_fit_supported(A, a._latent_dim, 1))
+               and _native.use_native_for(a.autoencoder.parts()[0].flat) for a in aes)
+
+
+@torch.no_grad()
+def _metrics_device(aes: list) -> list:
+    """The device path of ``AE.metrics_many`` (the caller has checked ``_metrics_device_ok``; a non-finite
+    panel still sends the whole call to the host methods).  Two jobs per AE: the in-sample panel as one
+    window under the identity scaler (``_x_train`` is scaled already), and the test panel's expanding
+    windows under refit scalers."""
+    import hashlib
+
+    nat = _native.native()
+    dev = aes[0].device
+    panels, by_id, tables = {}, {}, {}
+
+    def panel(obj):
+        # one upload per distinct panel of the call: by object first, then by content (every AE of a sweep
+        # holds its own, equal, scaled copy of the training rows)
+        if id(obj) not in by_id:
+            x = np.asarray(obj, dtype=np.float64)
+            key = (x.shape, hashlib.blake2b(np.ascontiguousarray(x).tobytes(), digest_size=16).digest())
+            if key not in panels:
+                if not np.isfinite(x).all():
+                    return None
+                # (A, n): one contiguous row per column, so that lanes striding the rows read coalesced
+                panels[key] = torch.as_tensor(np.ascontiguousarray(x.T), device=dev)
+            by_id[id(obj)] = key
+        return by_id[id(obj)]
+
+    def table(key, ends, refit):
+        tk = (key, ends, refit)
+        if tk not in tables:
+            e = torch.as_tensor(np.asarray(ends, dtype=np.int32), device=dev)
+            tables[tk] = (e,) + tuple(nat.ae_window_table(panels[key], e, refit))
+        return tables[tk]
+
+    jobs = []  # (panel, ends tensor, scale, min, ss_tot, We, Wd) per job; AE i owns jobs 2 i and 2 i + 1
+    rows = []  # per job: the rows of each window (the work list's sort key)
+    for a in aes:
+        enc, dec = a.autoencoder.parts()
+        nw = a._x_train.shape[1] * a._latent_dim
+        We, Wd = enc.flat.data[:nw].contiguous(), dec.flat.data[:nw].contiguous()
+        for obj, ends, refit in ((a._x_train, range(len(a._x_train), len(a._x_train) + 1), False),
+                                 (a._x_test, a._oos_ends(), True)):
+            key = panel(obj)
+            if key is None:
+                return _metrics_host(aes)
+            jobs.append((panels[key],) + table(key, ends, refit) + (We, Wd))
+            rows.append(np.asarray(ends, dtype=np.int64))
+    # one wave per (job, window), the heaviest windows first
+    jidx = np.concatenate([np.full(len(r), j, dtype=np.int32) for j, r in enumerate(rows)])
+    widx = np.concatenate([np.arange(len(r), dtype=np.int32) for r in rows])
+    order = np.argsort(-np.concatenate(rows), kind="stable")
+    work = torch.as_tensor(np.ascontiguousarray(np.stack([jidx[order], widx[order]], 1)), device=dev)
+    col = lambda i: [j[i] for j in jobs]  # noqa: E731
+    r2_t, rm_t = nat.ae_recon_metrics(col(0), col(1), col(2), col(3), col(4), col(5), col(6), work,
+                                      aes[0].dtype == torch.bfloat16)
+    both = torch.stack([r2_t, rm_t]).cpu().numpy()
+    cuts = np.cumsum([len(r) for r in rows])[:-1]
+    r2s, rms = np.split(both[0], cuts), np.split(both[1], cuts)
+    return [{"IS_r2": float(r2s[2 * i][0]), "IS_RMSE": float(rms[2 * i][0]),
+             "OOS_r2": r2s[2 * i + 1].tolist(), "OOS_RMSE": rms[2 * i + 1].tolist()} for i in range(len(aes))]
+
+
+def _metrics_host(aes: list) -> list:
+    """The per-AE host methods' values (``AE.metrics_many`` off the device path)."""
+    res = []
+    for a in aes:
+        a._metrics_cache = None  # (the host values, not an earlier cache)
+        res.append({"IS_r2": a.model_IS_r2(), "IS_RMSE": a.model_IS_RMSE(),
+                    "OOS_r2": a.model_OOS_r2(), "OOS_RMSE": a.model_OOS_RMSE()})
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # the AE replication object (reference API)
 # ------------------------------------------------------------------------------------------
 class AE:
@@ -206,6 +294,7 @@ class AE:
     # -- training ------------------------------------------------------------------------------
     def _new_trainer(self) -> AETrainer:
         self._oos_cache = None  # (predictions of the previous model)
+        self._metrics_cache = None  # (and its metrics: AE.metrics_many)
         self.autoencoder = FactorAutoencoder(self._latent_dim, self._x_train.shape[1], seed=self.seed, dtype=torch.float32,
                                              device=self.device)
         return AETrainer(self.autoencoder, device=self.device)
@@ -272,11 +361,49 @@ class AE:
         return self.autoencoder.encoder.predict(xt).double().cpu().numpy()
 
     # -- reconstruction metrics -------------------------------------------------------------------
+    # (each reads the cache that ``AE.metrics_many`` fills, else computes on the host as the reference does)
+    def _cached(self, key):
+        # (a cache filled under another ``oos_stride`` describes other windows: ignored)
+        c = getattr(self, "_metrics_cache", None)
+        return None if c is None or getattr(self, "_metrics_stride", None) != self.oos_stride else c[key]
+
     def model_IS_r2(self):
-        return r2_score(self._x_train, self._predict(self._x_train))
+        c = self._cached("IS_r2")
+        return r2_score(self._x_train, self._predict(self._x_train)) if c is None else c
 
     def model_IS_RMSE(self):
-        return rmse(self._x_train, self._predict(self._x_train))
+        c = self._cached("IS_RMSE")
+        return rmse(self._x_train, self._predict(self._x_train)) if c is None else c
+
+    def _oos_ends(self) -> range:
+        """The ends i of the expanding OOS windows xt[:i]."""
+        return range(2, len(self._x_test), self.oos_stride)
+
+    @staticmethod
+    def metrics_many(aes: list) -> list:
+        """``{"IS_r2", "IS_RMSE", "OOS_r2" (list), "OOS_RMSE" (list)}`` for every AE: what ``model_IS_r2``,
+        ``model_IS_RMSE``, ``model_OOS_r2`` and ``model_OOS_RMSE`` return, kept in a per-AE cache that those
+        methods read until the AE is retrained.
+
+        On a native GPU build (all AEs on one cuda device, fp32 or bf16, input width and latent size <= 32,
+        finite panels, ``HFREP_AE_METRICS_DEVICE`` not ``0``) every AE and every window is evaluated in one
+        launch chain of csrc/ae_eval.hip: each distinct panel is uploaded once, its refit scalers and
+        ss_tot come from ``ae_window_table``, and one wave per (AE, window) scales, predicts and reduces the
+        window's rows on the device.  The values agree with the host procedure within the compute dtype's
+        rounding noise (another summation order), not bitwise.  Otherwise: the per-AE host methods,
+        with exactly their values."""
+        import os
+
+        aes = list(aes)
+        if not aes:
+            return []
+        if os.environ.get("HFREP_AE_METRICS_DEVICE", "1") != "0" and _metrics_device_ok(aes):
+            res = _metrics_device(aes)
+        else:
+            res = _metrics_host(aes)
+        for a, r in zip(aes, res):
+            a._metrics_cache, a._metrics_stride = r, a.oos_stride
+        return res
 
     def _oos_windows(self):
         """(scaled window, prediction) for every expanding window xt[:i], i = 2 .. len - 1, each scaled by its
@@ -285,7 +412,7 @@ class AE:
         cached until the model is retrained."""
         if getattr(self, "_oos_cache", None) is None:
             xt = np.asarray(self._x_test, dtype=np.float64)
-            xrs = [MinMaxScaler().fit_transform(xt[:i]) for i in range(2, len(xt), self.oos_stride)]
+            xrs = [MinMaxScaler().fit_transform(xt[:i]) for i in self._oos_ends()]
             pred = self._predict(np.concatenate(xrs, 0)) if xrs else np.zeros((0, xt.shape[1]))
             cuts = np.cumsum([len(x) for x in xrs])[:-1]
             self._oos_cache = list(zip(xrs, np.split(pred, cuts)))
@@ -295,10 +422,12 @@ class AE:
         return [metric(xr, p) for xr, p in self._oos_windows()]
 
     def model_OOS_r2(self):
-        return self._oos(r2_score)
+        c = self._cached("OOS_r2")
+        return self._oos(r2_score) if c is None else list(c)
 
     def model_OOS_RMSE(self):
-        return self._oos(rmse)
+        c = self._cached("OOS_RMSE")
+        return self._oos(rmse) if c is None else list(c)
 
     # -- replication ---------------------------------------------------------------------------------
     def ante(self, rf, hfd, window=24):

@@ -45,21 +45,24 @@ def chronological_split(cleaned: dict, frac: float = 0.5):
 
 def latent_sweep(cleaned: dict, latents=range(1, 22), window: int = 24, frac: float = 0.5,
                  x_extra: np.ndarray | None = None, y_extra: np.ndarray | None = None, seed: int = 123,
-                 device="cpu", verbose: bool = False, dtype=None) -> SweepResult:
+                 device="cpu", verbose: bool = False, dtype=None, oos_stride: int = 1) -> SweepResult:
     """Train one autoencoder per latent size and evaluate it as a hedge-fund clone.
 
     ``x_extra`` / ``y_extra``: extra (generated) training rows appended to the real training rows
     (the augmented study); the test period is always real data.  ``device`` / ``dtype``: where and
     in which compute dtype the autoencoders train and predict (fp32 on the CPU by default; ``cuda``
     runs the engine's native Dense / optimizer kernels, BASELINE config 2).  On the GPU the sweep's
-    fits train in one launch (``AE.train_many``).
+    fits train in one launch (``AE.train_many``) and are evaluated in one pass (``AE.metrics_many``).
+    ``oos_stride``: one expanding OOS window every that many test rows (1 = the reference's every window).
     """
     return latent_sweep_many(cleaned, seeds=[seed], latents=latents, window=window, frac=frac,
-                             x_extras=[x_extra], y_extras=[y_extra], device=device, verbose=verbose, dtype=dtype)[0]
+                             x_extras=[x_extra], y_extras=[y_extra], device=device, verbose=verbose, dtype=dtype,
+                             oos_stride=oos_stride)[0]
 
 
 def latent_sweep_many(cleaned: dict, seeds, latents=range(1, 22), window: int = 24, frac: float = 0.5,
-                      x_extras=None, y_extras=None, device="cpu", verbose: bool = False, dtype=None) -> list:
+                      x_extras=None, y_extras=None, device="cpu", verbose: bool = False, dtype=None,
+                      oos_stride: int = 1) -> list:
     """``latent_sweep`` for several seeds (``x_extras[i]`` / ``y_extras[i]``: seed i's extra rows or None):
     every (seed, latent) autoencoder is built first and all of them train together (one csrc/ae.hip
     launch on a native GPU build), then each is evaluated.  Returns one SweepResult per seed."""
@@ -77,9 +80,10 @@ def latent_sweep_many(cleaned: dict, seeds, latents=range(1, 22), window: int = 
             xtr = np.vstack([xtr, xe])
             ytr = np.vstack([ytr, ye])
         for k in latents:
-            aes.append(AE(xtr, ytr, x_te, y_te, k, device=device, seed=s,
+            aes.append(AE(xtr, ytr, x_te, y_te, k, device=device, seed=s, oos_stride=oos_stride,
                           **({"dtype": dtype} if dtype is not None else {})))
     AE.train_many(aes)
+    AE.metrics_many(aes)  # (the IS / OOS metrics of every AE in one pass: the model_* calls below read them)
     out = []
     for si in range(len(seeds)):
         rows, s_ante, s_post, turns, posts = [], [], [], [], []
@@ -137,7 +141,9 @@ def daily_factor_study(daily: pd.DataFrame, latents=range(1, 22), seeds=(123,), 
     native GPU build (``AE.train_many``).  Returns one row per (seed, latent): in-sample R^2 / RMSE on
     the training days, the mean out-of-sample R^2 / RMSE over expanding test windows (one every
     ``oos_stride`` trading days, each with its own refit scaler, the reference's OOS procedure), the
-    epochs run, and the wall time of the batched fit (``fit_s``, the same for every row)."""
+    epochs run, and the wall times of the batched fit and of the evaluation of all of them
+    (``fit_s`` / ``eval_s``, the same for every row; ``AE.metrics_many``: one device pass on a native GPU
+    build, where ``oos_stride=1``, the reference's every window, is affordable too)."""
     import time
 
     x = daily.to_numpy(np.float64)
@@ -155,10 +161,14 @@ def daily_factor_study(daily: pd.DataFrame, latents=range(1, 22), seeds=(123,), 
 
         torch.cuda.synchronize()
     fit_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    AE.metrics_many(aes)  # (its results come back to the host: no synchronize needed)
+    eval_s = time.perf_counter() - t0
     rows = []
     for i, ae in enumerate(aes):
         rows.append({"seed": seeds[i // len(list(latents))], "latent": ae._latent_dim,
                      "IS_r2": float(ae.model_IS_r2()), "IS_RMSE": float(ae.model_IS_RMSE()),
                      "OOS_r2": float(np.mean(ae.model_OOS_r2())), "OOS_RMSE": float(np.mean(ae.model_OOS_RMSE())),
-                     "epochs": len(ae.history["loss"]), "fit_s": fit_s, "train_rows": n, "test_rows": len(x_te)})
+                     "epochs": len(ae.history["loss"]), "fit_s": fit_s, "eval_s": eval_s, "train_rows": n,
+                     "test_rows": len(x_te)})
     return pd.DataFrame(rows)
