@@ -73,7 +73,7 @@ bool launch_lstmf_tbwd(const float* dH, const float* dHd, const float* tape, con
 // K <= 36 take; default); returns the previous setting
 int set_lstmf_fwd_impl(int v);  // 1: exact-fp32 forward everywhere, 2 / 3: the split-recurrent one for K <= 36
 int set_lstmf_fwd100_impl(int v);  // K = 100 forward, whatever the switch above: 1 four waves (lstmf_fwd_kernel), 2 eight waves (lstmf_fwd2_kernel; default, same bits)
-int set_lstmf_bwd_impl(int v);  // 2: the exact-fp32 BPTT kernel, 3: the split-recurrent one
+int set_lstmf_bwd_impl(int v);  // 2: the exact-fp32 BPTT kernel, 3: the split-recurrent one on four waves (lstmf_bwds_kernel), 4: on eight waves, two per SIMD, for the launches that keep no h adjoints (lstmf_bwds2_kernel; default, same bits as 3) and 3 for those that do
 
 // ---- lstmf_grad.hip (fp32 LSTM gradient GEMMs; shared device helpers: lstmf_dev.h) ----
 // fused fp32 LSTM weight gradients (K in {32, 35, 36, 100}, H = 100, N = 400): gW += X^T dZ (+ Xd^T dZd),

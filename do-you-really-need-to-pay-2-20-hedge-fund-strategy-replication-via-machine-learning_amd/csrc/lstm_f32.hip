@@ -42,6 +42,8 @@
 // tangent step loads, the HEAD row factors and the padded-unit mask from one definition each ("stages the
 // reverse kernels share", above the kernels); the tangent cell adjoint is a helper in lstmf_tbwdp and
 // written out in lstmf_tbwd1, whose bits it would change.
+// lstmf_bwds2 is lstmf_bwds on eight waves, two per SIMD (seven tile waves and one wave with the dZ stores; same
+// bits): the default BPTT where no h adjoints are kept (set_lstmf_bwd_impl 4; profiles/bwds_two_wave/README.md).
 #include "lstmf_dev.h"
 
 #include <atomic>
@@ -2033,6 +2035,238 @@ lstmf_bwds_kernel(const float* __restrict__ dH, const float* __restrict__ tape, 
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// The split BPTT on 8 waves, two per SIMD: lstmf_bwds2_kernel
+// ------------------------------------------------------------------------------------------
+// lstmf_bwds_kernel runs one wave per SIMD, and that wave issues its 156 MFMAs, seven cells' VALU and
+// transcendentals, the plane split, the tape loads and the dZ stores in program order: every s_waitcnt, LDS
+// latency or barrier wait leaves its SIMD idle, and one of the eight dh_rec tiles is padding (units 112..127).
+// Here the work goes to 8 waves, waves v and v + 4 sharing a SIMD:
+//   * MFMA tiles: wave v < 7 owns the one real 16-column tile v of dh_rec = dz U^T (columns 16 v .. 16 v + 15;
+//     tile e of wave w there is tile 2 w + e here) for all 13 k-steps, its U^T planes in 156 registers, one
+//     accumulator chain from zero per half-phase in that kernel's order (mma_split6 over ks = 0..12); wave 7 has
+//     no tile and the padding tile is gone;
+//   * cells: the 25 real cell groups (4 units x 16 rows; group gt = units 4 gt .. 4 gt + 3 = group gt % 7 of wave
+//     gt / 7 there) go by threes, wave v < 7 groups 3 v .. 3 v + 2 and wave 7 groups 21 .. 24: a SIMD carries two
+//     tiles and six groups (SIMDs 0..2) or one tile and seven groups (SIMD 3), split 3 + 3 or 3 + 4 over its waves;
+//   * dZ stores: all on wave 7, the wave without a tile (lane l: the 16-byte chunks l and, l < 36, l + 64 of every
+//     row of the half); on the tile waves the store data and addresses cost the registers that U^T needs
+//     (profiles/bwds_two_wave/README.md).
+// The tape keeps the four-wave lane-native layout and a group addresses its slots, its dH words, the head
+// weight and its dz / plane / ht words through its global index.  There is no AHD form: with the h adjoints kept the
+// eight-wave kernel measured no clear gain per call (profiles/bwds_two_wave/README.md), so those launches stay on
+// lstmf_bwds_kernel under every value of the switch.  The LDS images, the row-half pipeline
+//   P1(t): B(0, t) + A(1, t)      P2(t): B(1, t) + A(0, t - 1)
+// and the LDS-only barrier per half-phase are lstmf_bwds_kernel's; a cell reads ht words and writes dz words of
+// the row half the MFMAs of the phase do not touch, so any ownership of tiles and groups is race-free between two
+// barriers.  Each role (a tile and 3 groups; no tile, 4 groups and the stores) is its own straight-line
+// instantiation behind one branch on the wave index at kernel entry.  dZ is bitwise lstmf_bwds_kernel's
+// (tests/test_bwds_two_wave_gpu.py).
+
+// the dz tile -> dZ[:, t, :] from ONE wave: lane l owns the 16-byte chunks l and l + 64 (l < 36; the others store
+// out of range) of every row, the row in the uniform offset
+struct RevStoreW {
+  int lo[2], go[2];
+  __device__ __forceinline__ RevStoreW(int lane, int Tn) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const bool ok = lane + 64 * j < 100;
+      const int ch = ok ? lane + 64 * j : lane, qq = ch / 25, c = ch - 25 * qq;
+      lo[j] = qq * BZ_KQ + 4 * c;
+      go[j] = ok ? (qq * FH + 4 * c) * 4 : kOOB;
+    }
+  }
+  // rows of half M of `tile` (holding dz at step ts) -> dZ[:, ts, :], as RevStore::half
+  template <int M>
+  __device__ __forceinline__ void half(const float* tile, rsrc_t rz, int Tn, int ts, int nr) const {
+#pragma unroll
+    for (int r = 16 * M; r < 16 * M + 16; ++r) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(tile + lo[j] + r * BZ_LR);
+        st16(v, rz, r < nr, go[j], (r * Tn + ts) * FG * 4);
+      }
+    }
+  }
+};
+
+#ifndef HFREP_BWDS2_NAF
+// A-fragment register sets of a tile wave: 2 (the next k-step's reads under this one's MFMAs) spills 320-500 B
+#define HFREP_BWDS2_NAF 1
+#endif
+template <int ACT, bool HEAD, int NG, bool TILE, bool ST>
+__device__ __forceinline__ void bwds2_run(const float* __restrict__ dH, const float* __restrict__ tape,
+                                          const float* __restrict__ U, float* __restrict__ dZ, int B, int Tn,
+                                          const float* __restrict__ hd, const float* __restrict__ hw, float* fsm,
+                                          int v) {
+  float* zt = fsm;                                     // fp32 dz tile [32][BZ_LR]: [q][u'] per row
+  float* ht = zt + 32 * BZ_LR;                         // dh_rec tile [32][BH_LR]
+  float* trash = ht + 32 * BH_LR;                      // [4 * BZ_KQ + 4] padding words (every group here is real)
+  lds_char* zp = (lds_char*)(trash + 4 * BZ_KQ + 4);   // dz planes [3][32][BS_LZ] bf16
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int q = lane & 3, g = lane >> 4, j4 = (lane & 15) >> 2, c16 = lane & 15;
+  const int nrb = (B + 31) / 32;
+  const int g0 = 3 * v;  // first cell group of this wave (uniform)
+  // U^T planes of tile v: B[k = 32 ks + 8 g + j][col 16 v + c16] = U[col][(k & 3) H + (k >> 2)]
+  bf16x8 up[TILE ? DS_KS : 1][3];
+  if constexpr (TILE) {
+    const int col = 16 * v + c16;
+    const bool ok = col < FH;
+#pragma unroll
+    for (int ks = 0; ks < DS_KS; ++ks) {
+      f32x4 uv[2];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = min(32 * ks + 8 * g + j, FG - 1);
+        const float x = U[(ok ? col : 0) * FG + (k & 3) * FH + (k >> 2)];
+        uv[j >> 2][j & 3] = (ok && 32 * ks + 8 * g + j < FG) ? x : 0.f;
+      }
+      uint32_t p0[3][2], p1[3][2];
+      split3(uv[0], p0);
+      split3(uv[1], p1);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        up[ks][p] = __builtin_bit_cast(bf16x8, make_uint4(p0[p][0], p0[p][1], p1[p][0], p1[p][1]));
+        // (no AGPR pin: a kernel that names AGPRs gets its 256 registers as 128 V + 128 A and spills)
+        asm volatile("" : "+v"(up[ks][p]));
+      }
+    }
+  }
+  const int ub = 4 * g0 + j4;  // unit of group 0 in this lane; group k adds 4 k
+  const int hr = (4 * g + q) * BH_LR + ub, zw = (4 * g + q) * BZ_LR + ub;  // (+16 m rows, + 4 k units)
+  const int zpw = ((4 * g + q) * BS_LZ + 4 * ub) * 2;                    // plane word (+ 32 k bytes)
+  const int ao = (c16 * BS_LZ + 8 * g) * 2;  // A fragment: row c16 (+ 16 M), k = 32 ks + 8 g .. + 7
+  const RevStoreW st(lane, Tn);              // (used by the store role alone)
+  const int tl = lane * 16, tcl = (256 + lane) * 4;
+  int tsl[NG];  // tape slot of group k, row half 0: the four-wave kernel's (w, n) = (gt / 7, gt % 7) (bytes, uniform)
+#pragma unroll
+  for (int k = 0; k < NG; ++k) tsl[k] = ftape_lane((g0 + k) / FNT, 0) + ftape_slot(0, (g0 + k) % FNT);
+  for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const int row0 = rb * 32;
+    const rsrc_t rdh = ftile_rsrc(dH, row0, B, Tn, FH), rt = ftape_rsrc(tape, rb, nrb, Tn);
+    const rsrc_t rz = ftile_rsrc(dZ, row0, B, Tn, FG);
+    const int nr = min(32, B - row0);
+    int vp1[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) vp1[m] = ((16 * m + 4 * g + q) * Tn * FH + ub) * 4;
+    float hdv[2];
+    head_rows<HEAD>(hdv, hd, true, row0, B, g, q);  // (the launcher selects HEAD by hd)
+    const rsrc_t rhw = head_rsrc<HEAD>(hw, Tn);
+    const int hvo = ub * 4;
+    float dc[2][NG], tc[2][NG];
+    f32x4 tg[NG];
+    float tcp[NG], tdh[NG];
+    const int T1 = Tn - 1;
+#pragma unroll
+    for (int k = 0; k < NG; ++k) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        dc[m][k] = 0.f;
+        tc[m][k] = ld1(rt, tcl, T1 * FT_STEP * 4 + m * ftape_slot(1, 0) + tsl[k]);  // c_{T-1}
+      }
+      bwdf_tape_load_u<HEAD>(tg[k], tcp[k], tdh[k], rt, rdh, tl, tcl, vp1[0], T1 * FT_STEP * 4 + tsl[k],
+                             max(T1 - 1, 0) * FT_STEP * 4 + tsl[k], T1 * FH * 4 + 16 * k, true, T1 > 0, hdv[0], rhw, hvo);
+    }
+    // dz_T = 0 (planes, pad columns k >= 400 included), dh_rec(T - 1) = 0
+    for (int i = tid; i < 3 * BS_PL / 16; i += 512)
+      reinterpret_cast<__attribute__((address_space(3))) u32x4_t*>(zp)[i] = u32x4_t{0, 0, 0, 0};
+    for (int i = tid; i < 32 * BH_LR; i += 512) ht[i] = 0.f;
+    __syncthreads();
+    // cell adjoint of (row half M, group k) at step t, then the loads for the set's next use
+    auto cell = [&](auto M_, int k, float hrec, int t) {
+      constexpr int m = decltype(M_)::value;
+      f32x4 z4;
+      bptt_cell<ACT>(z4, dc[m][k], tg[k], tc[m][k], tcp[k], tdh[k], hrec, true, zt + zw + 16 * m * BZ_LR + 4 * k, trash);
+      uint32_t p[3][2];
+      split3(z4, p);
+      planes_store(p, zp + zpw + 16 * m * BS_LZ * 2 + 32 * k, BS_PL);
+      tc[m][k] = tcp[k];  // c_{t-1} is the next step's c
+      const int sl = (1 - m) * ftape_slot(1, 0) + tsl[k];  // the set's next use is the other row half
+      if constexpr (m == 0) {  // next use: B(1, t)
+        bwdf_tape_load_u<HEAD>(tg[k], tcp[k], tdh[k], rt, rdh, tl, tcl, vp1[1], t * FT_STEP * 4 + sl,
+                               max(t - 1, 0) * FT_STEP * 4 + sl, t * FH * 4 + 16 * k, true, t > 0, hdv[1], rhw, hvo);
+      } else {  // next use: B(0, t - 1)
+        const int tp = t > 0 ? t - 1 : 0;
+        bwdf_tape_load_u<HEAD>(tg[k], tcp[k], tdh[k], rt, rdh, tl, tcl, vp1[0], tp * FT_STEP * 4 + sl,
+                               max(tp - 1, 0) * FT_STEP * 4 + sl, tp * FH * 4 + 16 * k, t > 0, tp > 0, hdv[0], rhw, hvo);
+      }
+    };
+    // one half-phase: dz rows of half MA out to HBM (store role), the cells of half 1 - MA at step t, and rows MA
+    // of this wave's tile of dh_rec = dz[rows MA] U^T (the planes hold dz_{t + 1} there for MA = 1, dz_t for MA = 0)
+    auto phase = [&](auto MA_, int t) {
+      constexpr int MA = decltype(MA_)::value;
+      if constexpr (ST) {
+        if constexpr (MA == 1) {
+          if (t < T1) st.half<1>(zt, rz, Tn, t + 1, nr);
+        } else {
+          st.half<0>(zt, rz, Tn, t, nr);
+        }
+      }
+      float hv[NG];  // the cells' dh_rec words (rows of half 1 - MA, completed in the previous phase)
+#pragma unroll
+      for (int k = 0; k < NG; ++k) hv[k] = ht[hr + 16 * (1 - MA) * BH_LR + 4 * k];
+      if constexpr (TILE) {
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        const lds_char* ar = zp + ao + 16 * MA * BS_LZ * 2;
+        constexpr int NAF = HFREP_BWDS2_NAF;
+        bf16x8 af[NAF][3];
+        if constexpr (NAF == 2) {
+#pragma unroll
+          for (int p = 0; p < 3; ++p) af[0][p] = *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(ar + p * BS_PL);
+        }
+#pragma unroll
+        for (int ks = 0; ks < DS_KS; ++ks) {
+          const int kr = NAF == 2 ? ks + 1 : ks;  // the k-step whose fragments are read here
+          if (kr < DS_KS) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+              af[kr % NAF][p] = *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(ar + p * BS_PL + 64 * kr);
+          }
+          acc = mma_split6(af[ks % NAF], up[ks], acc);
+          if (ks < NG) cell(std::integral_constant<int, 1 - MA>{}, ks, hv[ks], t);  // (compile-time)
+        }
+        // one schedule for the whole phase: per k-step its A fragments, then its 6 MFMAs with 3 VALU slots (the
+        // cells' math) after each one; loads and LDS stores of the cells go where they fit
+#pragma unroll
+        for (int ks = 0; ks < DS_KS; ++ks) {
+          __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+#pragma unroll
+          for (int i = 0; i < 6; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // rows 16 MA + 4 g + i, column 16 v + c16
+        float* hp = ht + (16 * MA + 4 * g) * BH_LR + 16 * v + c16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hp[i * BH_LR] = acc[i];
+      } else {
+#pragma unroll
+        for (int k = 0; k < NG; ++k) cell(std::integral_constant<int, 1 - MA>{}, k, hv[k], t);
+      }
+      lds_barrier();
+    };
+    for (int t = T1; t >= 0; --t) {
+      phase(I1{}, t);  // P1(t): B(0, t) + A(1, t)
+      phase(I0{}, t);  // P2(t): B(1, t) + A(0, t - 1)
+    }
+    if constexpr (ST) st.half<1>(zt, rz, Tn, 0, nr);
+    __syncthreads();  // (the tiles are re-zeroed for the next row block)
+  }
+}
+
+template <int ACT, bool HEAD = false>
+__global__ void __launch_bounds__(512, 1)
+lstmf_bwds2_kernel(const float* __restrict__ dH, const float* __restrict__ tape, const float* __restrict__ U,
+                   float* __restrict__ dZ, int B, int Tn, const float* __restrict__ hd, const float* __restrict__ hw) {
+  extern __shared__ __attribute__((aligned(16))) float fsm[];
+  const int v = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (v < 7) bwds2_run<ACT, HEAD, 3, true, false>(dH, tape, U, dZ, B, Tn, hd, hw, fsm, v);
+  else bwds2_run<ACT, HEAD, 4, false, true>(dH, tape, U, dZ, B, Tn, hd, hw, fsm, v);
+}
+
 // ==========================================================================================
 // host side
 // ==========================================================================================
@@ -2153,9 +2387,11 @@ bool launch_lstmf_tfwd(const float* xd, const float* W, const float* U, const fl
   return fwdf_k<true, true>(K, act, xd, W, nullptr, U, tape, hds, ttape, B, Tn, s);
 }
 
-// BPTT: 2 the exact-fp32 role split (lstmf_bwdp_kernel), 3 the split-recurrent BPTT (lstmf_bwds_kernel)
+// BPTT: 2 the exact-fp32 role split (lstmf_bwdp_kernel), 3 the split-recurrent BPTT on four waves
+// (lstmf_bwds_kernel, the bitwise reference of 4), 4 the split-recurrent BPTT on two waves per SIMD where it is
+// instantiated (lstmf_bwds2_kernel: without the kept h adjoints; same bits) and 3 elsewhere
 static std::atomic<int>& bwdf_impl() {
-  static std::atomic<int> v{fp32_exact() ? 2 : 3};
+  static std::atomic<int> v{fp32_exact() ? 2 : 4};
   return v;
 }
 template <int ACT>
@@ -2164,6 +2400,16 @@ void bwdf_launch(const float* dH, const float* tape, const float* U, float* dZ, 
   const int ver = bwdf_impl().load(std::memory_order_relaxed);
   const int nrb = (B + 31) / 32, cus = device_cu_count();
   const size_t sm = (size_t)(32 * BZ_LR + 32 * BH_LR + 4 * BZ_KQ) * 4;
+  if (ver == 4 && !aH) {  // (with aH kept: the four-wave kernel below)
+    auto go = [&](auto k) {
+      allow_lds(reinterpret_cast<const void*>(k));
+      hipLaunchKernelGGL(k, dim3(nrb < cus ? nrb : cus), dim3(512), sm + 16 + 3 * BS_PL, s, dH, tape, U, dZ, B, Tn, hd,
+                         hw);
+    };
+    if (hd) go(lstmf_bwds2_kernel<ACT, true>);
+    else go(lstmf_bwds2_kernel<ACT, false>);
+    return;
+  }
   if (ver != 2) {
     auto go = [&](auto k) {
       allow_lds(reinterpret_cast<const void*>(k));

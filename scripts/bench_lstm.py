@@ -41,8 +41,15 @@ def main():
     ap.add_argument("--fwd-impl", type=int, default=0, help="fp32: set_lstmf_fwd_impl value (0: the library default)")
     ap.add_argument("--fwd100-impl", type=int, default=0,
                     help="fp32, K = 100: set_lstmf_fwd100_impl value (1 four waves, 2 eight waves; 0: the library default)")
+    ap.add_argument("--bwd-impl", type=int, default=0,
+                    help="fp32: set_lstmf_bwd_impl value (2 exact, 3 split on four waves, 4 split on eight waves; "
+                         "0: the library default)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.bwd_impl:
+        from hfrep.ops import _native
+
+        _native.native().set_lstmf_bwd_impl(a.bwd_impl)
     if a.fwd_impl:
         from hfrep.ops import _native
 
@@ -76,13 +83,20 @@ def main():
         "wgrad": lambda: Fn.lstm_wgrad_(x, hs, dZ_, gW, gU, gb),
         "wgrad_tan": lambda: Fn.lstm_wgrad_(x, hs, dZ_, gW, gU, gb, xd, hds, dZ_),
     }
+    if a.dtype == "float32":  # the BPTT's other instantiations: in-kernel head adjoint (HEAD), kept h adjoints (AHD)
+        hd, hw = torch.randn(B, 1, device=dev, generator=g), torch.randn(T * H, 1, device=dev, generator=g)
+        oa = Fn.OuterAdjoint(hd, hw, (B, T, H))
+        ops["bwd_head"] = lambda: Fn.lstm_layer_bwd(oa, tape, U, a.act)
+        ops["bwd_ah"] = lambda: Fn.lstm_layer_bwd_keep(dH, tape, U, a.act)
+        ops["bwd_head_ah"] = lambda: Fn.lstm_layer_bwd_keep(oa, tape, U, a.act)
     if "tbwd1" in a.only.split(","):  # fp32 only: the single-stream tangent reverse, a_hd from a kept BPTT
         ahd = Fn.lstm_layer_bwd_keep(dHd, tape, U, a.act)[2]
         ops["tbwd1"] = lambda: Fn.lstm_layer_tbwd1(dH, ahd, tape, ttape, U, a.act)
     for name in a.only.split(","):
         for _ in range(a.repeats):
             ms = timeit(ops[name], a.iters)
-            print(json.dumps({"op": name, "dtype": a.dtype, "B": B, "T": T, "K": K, "act": a.act, "fwd_impl": a.fwd_impl, "fwd100_impl": a.fwd100_impl, "ms": round(ms, 4),
+            print(json.dumps({"op": name, "dtype": a.dtype, "B": B, "T": T, "K": K, "act": a.act, "fwd_impl": a.fwd_impl, "fwd100_impl": a.fwd100_impl,
+                              "bwd_impl": a.bwd_impl, "ms": round(ms, 4),
                               "us_per_step": round(ms * 1e3 / T, 2)}), flush=True)
 
 
