@@ -269,6 +269,21 @@ void launch_nb_divergences(const float* real, const float* fake, const double* t
 int lp_blocks(int64_t n);
 void launch_lp_cols(const float* a, const float* b, double* slab, double* out, int64_t n, int F, hipStream_t s);
 
+// ---- conv1d.hip: direct causal conv1d (no unfolded tensor in HBM).  x (B, T, C_in) / dz, y (B, T, C_out) in
+//      dt, W / gW fp32 (k, C_in, C_out), tap j at time offset (k - 1 - j) dil.  false = shape not supported
+//      (C_in % 4 == 0, 4 <= C_in <= 128; C_out % 4 == 0, 96 < C_out <= 128; k <= 8; the weight operand of
+//      every tap beside a 64-row tile within one CU's LDS; any dil >= 1, any B, T). ----
+bool conv1d_supported(int dt, int Cin, int Cout, int k, int dil);
+bool launch_conv1d_fwd(int dt, const void* x, const float* W, const float* bias, void* y, int B, int Tn, int Cin,
+                       int Cout, int k, int dil, int act, hipStream_t s);
+bool launch_conv1d_dgrad(int dt, const void* dz, const float* W, void* dx, int B, int Tn, int Cin, int Cout, int k,
+                         int dil, hipStream_t s);
+// gW += ..., gb += ... (gb may be null) through per-workgroup slabs in ws (every element written) and a
+// fixed-order reduce
+size_t conv1d_wgrad_workspace_floats(int B, int Tn, int Cin, int Cout, int k, bool has_bias);
+bool launch_conv1d_wgrad(int dt, const void* x, const void* dz, float* gW, float* gb, int B, int Tn, int Cin, int Cout,
+                         int k, int dil, float* ws, hipStream_t s);
+
 // ---- p2p.hip: one-shot all-reduce over IPC-mapped peer buffers (layout in p2p.hip) ----
 constexpr int kP2PMaxRanks = 8, kP2PMaxBlocks = 256;
 constexpr int kP2PCtr = 0, kP2PDone = 128, kP2PErr = 256, kP2PFlags = 4096, kP2PData = 16384;

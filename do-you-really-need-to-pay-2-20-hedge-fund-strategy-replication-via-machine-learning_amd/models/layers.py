@@ -355,8 +355,11 @@ class Flatten(Layer):
 class Conv1D(Layer):
     """Causal temporal convolution (K14 north-star variant; not used by the reference scripts).
 
-    Implemented as im2col + the native GEMM: kernel (K, C_in, C_out) is viewed as a Dense kernel
-    (K*C_in, C_out) over unfolded windows, so every explicit-engine method reuses Dense's.
+    Kernel (K, C_in, C_out), tap j at the time offset (K - 1 - j) * dilation.  The engine methods go through
+    ``Fn.conv1d_fwd`` / ``conv1d_dgrad`` / ``conv1d_wgrad_``: the direct gfx950 kernels (csrc/conv1d.hip, no
+    unfolded tensor; the context holds x and y only) where ``Fn.conv1d_direct`` says so, else im2col + the
+    native GEMMs with the kernel viewed as a Dense kernel (K*C_in, C_out) over unfolded windows, whose
+    ``cols`` the context keeps for the weight gradient.
     """
 
     kind = "conv1d"
@@ -377,40 +380,39 @@ class Conv1D(Layer):
         return R.conv1d_causal(x, self.w("kernel"), self.w("bias"), self.act, self.dil)
 
     def _unfold(self, x):
-        return Fn.im2col_causal(x, self.k, self.dil)
+        """``im2col_causal(x)`` for the unfolded route, None where the direct kernels run."""
+        return None if Fn.conv1d_direct(x, self.p("kernel"), self.dil) else Fn.im2col_causal(x, self.k, self.dil)
 
     def efwd(self, x, save):
         cols = self._unfold(x)
-        y = Fn.linear(cols, self.p("kernel").reshape(-1, self.filters), self.p("bias"), self.act_code)
-        return y, ({"x": x, "cols": cols, "y": y} if save else None)
+        y = Fn.conv1d_fwd(x, self.p("kernel"), self.p("bias"), self.act_code, self.dil, cols=cols)
+        if not save:
+            return y, None
+        return y, ({"x": x, "y": y} if cols is None else {"x": x, "cols": cols, "y": y})
 
     def ebwd(self, ctx, dy, need_dx, wgrad=True):
         dz = Fn.act_backward(dy, ctx["y"], self.act_code)
         if wgrad:
-            Fn.run_wgrad(Fn.linear_wgrad_, ctx["cols"], dz, self.g("kernel").reshape(-1, self.filters), self.g("bias"))
-        if not need_dx:
-            return None
-        dcols = Fn.linear_dgrad(dz, self.p("kernel").reshape(-1, self.filters))
-        return Fn.col2im_causal(dcols, self.k, self.dil, self.cin)
+            Fn.run_wgrad(Fn.conv1d_wgrad_, ctx["x"], dz, self.g("kernel"), self.g("bias"), self.dil, cols=ctx.get("cols"))
+        return Fn.conv1d_dgrad(dz, self.p("kernel"), self.dil) if need_dx else None
 
     def etfwd(self, ctx, xd):
         cols_d = self._unfold(xd)
-        zd = Fn.linear(cols_d, self.p("kernel").reshape(-1, self.filters), None, 0)
-        return Fn.act_backward(zd, ctx["y"], self.act_code), {"cols_d": cols_d, "zd": zd}
+        zd = Fn.conv1d_fwd(xd, self.p("kernel"), None, 0, self.dil, cols=cols_d)
+        return (Fn.act_backward(zd, ctx["y"], self.act_code),
+                {"xd": xd, "zd": zd} if cols_d is None else {"cols_d": cols_d, "zd": zd})
 
     def etbwd(self, ctx, tctx, dy, dyd, need_dx, need_dxd=True):
-        Wk = self.p("kernel").reshape(-1, self.filters)
-        gk = self.g("kernel").reshape(-1, self.filters)
+        Wk, gk = self.p("kernel"), self.g("kernel")
         if dy is None:
             dy = torch.zeros_like(ctx["y"])
         dzd = Fn.act_backward(dyd, ctx["y"], self.act_code)
         dz = Fn.act_tangent_backward(dy, dyd, ctx["y"], tctx["zd"], self.act_code)
-        Fn.run_wgrad(Fn.linear_wgrad_, ctx["cols"], dz, gk, self.g("bias"))
-        Fn.run_wgrad(Fn.linear_wgrad_, tctx["cols_d"], dzd, gk, None)
+        Fn.run_wgrad(Fn.conv1d_wgrad_, ctx["x"], dz, gk, self.g("bias"), self.dil, cols=ctx.get("cols"))
+        Fn.run_wgrad(Fn.conv1d_wgrad_, tctx.get("xd"), dzd, gk, None, self.dil, cols=tctx.get("cols_d"))
         if not need_dx:
             return None, None
-        return (Fn.col2im_causal(Fn.linear_dgrad(dz, Wk), self.k, self.dil, self.cin),
-                Fn.col2im_causal(Fn.linear_dgrad(dzd, Wk), self.k, self.dil, self.cin) if need_dxd else None)
+        return (Fn.conv1d_dgrad(dz, Wk, self.dil), Fn.conv1d_dgrad(dzd, Wk, self.dil) if need_dxd else None)
 
 
 def _init_tensor(spec: ParamSpec, gen, layer: Layer) -> torch.Tensor:

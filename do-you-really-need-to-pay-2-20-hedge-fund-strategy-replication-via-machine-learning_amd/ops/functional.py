@@ -11,6 +11,7 @@ dtype of the explicit engine); gradients are always fp32.
 from __future__ import annotations
 
 import contextlib
+import os
 
 import torch
 
@@ -264,6 +265,70 @@ def col2im_causal(dcols: torch.Tensor, k: int, dil: int, C: int) -> torch.Tensor
     for j in range(k):
         dxp[:, j * dil:j * dil + T] += dcols[:, :, j * C:(j + 1) * C]
     return dxp[:, pad:]
+
+
+# ---------------------------------------------------------------------------------------
+# causal conv1d: direct kernels (csrc/conv1d.hip) where they apply, else im2col + the GEMM family
+# ---------------------------------------------------------------------------------------
+# x (B, T, C_in), W (k, C_in, C_out) fp32 master kernel, tap j at the time offset (k - 1 - j) * dil.
+# The direct kernels stage a row tile with its halo in LDS and never write the unfolded (B, T, k C_in)
+# tensor; CPU tensors, shapes conv1d_supported declines and HFREP_CONV_DIRECT=0 take the unfolded route.
+
+
+def conv1d_direct(x: torch.Tensor, W: torch.Tensor, dil: int) -> bool:
+    """Whether the conv1d_* functions run the direct kernels for this input and kernel."""
+    if x.dim() != 3 or W.dim() != 3 or x.dtype not in (torch.bfloat16, torch.float32) or not _nat(x):
+        return False
+    if os.environ.get("HFREP_CONV_DIRECT", "1") == "0":
+        return False
+    k, cin, cout = W.shape
+    return bool(_ops().conv1d_supported(int(cin), int(cout), int(k), int(dil), x.dtype))
+
+
+def conv1d_wgrad_direct(x: torch.Tensor, gW: torch.Tensor, dil: int) -> bool:
+    """Whether conv1d_wgrad_ runs the direct weight-gradient kernel: fp32 only.  In bf16 the kernel measured slower
+    than im2col + the bf16 weight-gradient GEMM (profiles/conv1d_direct/README.md), so bf16 unfolds x for this one
+    product (a transient copy: nothing unfolded is saved between the passes) and runs the GEMM."""
+    return x is not None and x.dtype == torch.float32 and conv1d_direct(x, gW, dil)
+
+
+def _cv_in(t: torch.Tensor) -> torch.Tensor:
+    # the direct kernels stage rows with 16-byte loads: a contiguous view at an odd offset is copied
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def conv1d_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, act: int, dil: int,
+               cols: torch.Tensor | None = None) -> torch.Tensor:
+    """act(bias + sum_j x[t - (k-1-j) dil] @ W[j]) with zeros before each sample's first step.  ``cols``: the
+    caller's ``im2col_causal(x)`` (it keeps it for the weight gradient): the unfolded route runs on it."""
+    k, _, cout = W.shape
+    if cols is None and conv1d_direct(x, W, dil):
+        return _ops().conv1d_causal_fwd(_cv_in(x), W, b, int(dil), int(act))
+    if cols is None:
+        cols = im2col_causal(x, k, dil)
+    return linear(cols, W.reshape(-1, cout), b, act)
+
+
+def conv1d_dgrad(dz: torch.Tensor, W: torch.Tensor, dil: int) -> torch.Tensor:
+    """dx[t] = sum_j dz[t + (k-1-j) dil] @ W[j]^T with zeros past each sample's last step."""
+    k, cin, cout = W.shape
+    if conv1d_direct(dz, W, dil):
+        return _ops().conv1d_causal_dgrad(_cv_in(dz), W, int(dil))
+    return col2im_causal(linear_dgrad(dz, W.reshape(-1, cout)), k, dil, cin)
+
+
+def conv1d_wgrad_(x: torch.Tensor | None, dz: torch.Tensor, gW: torch.Tensor, gb: torch.Tensor | None, dil: int,
+                  cols: torch.Tensor | None = None) -> None:
+    """gW[j] += sum_{b, t} x[b, t - (k-1-j) dil]^T dz[b, t]; gb += sum dz.  ``cols``: the saved unfolded x
+    (the unfolded route; x is then unused)."""
+    k, _, cout = gW.shape
+    if cols is None and conv1d_wgrad_direct(x, gW, dil):
+        _ops().conv1d_causal_wgrad_(_cv_in(x), _cv_in(dz), gW, gb, int(dil))
+        return
+    if cols is None:
+        cols = im2col_causal(x, k, dil)
+    linear_wgrad_(cols, dz, gW.reshape(-1, cout), gb)
 
 
 # ---------------------------------------------------------------------------------------
