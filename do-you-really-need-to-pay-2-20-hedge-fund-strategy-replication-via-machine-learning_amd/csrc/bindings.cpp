@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 std::atomic<bool>& hfrep::poison_flag() {
   static std::atomic<bool> f{[] {
@@ -57,6 +58,63 @@ using hfrep::poison_flag;
 bool set_debug_poison(bool on) { return poison_flag().exchange(on); }
 
 // ------------------------------------------------------------------------------------ GEMM
+// Dense routing: the kernel each Dense op runs for a dtype and a shape.  The ops below switch on these,
+// and dense_route() prints them for the tests.
+// forward y (M, N) = act(x (M, K) W (K, N) + b)
+hfrep::DenseRoute linear_route(int dt, int K, int N) {
+  if (hfrep::skinny_supported(K, N)) return {hfrep::DK_SKINNY};
+  if (dt == hfrep::DT_F32 && hfrep::narrowf_supported(K, N)) return hfrep::narrowf_route(K, N);
+  if (dt == hfrep::DT_F32 && hfrep::widef_supported(K, N)) return hfrep::widef_route(K, N);
+  if (dt == hfrep::DT_BF16 && hfrep::narrow_supported(K, N)) return {hfrep::DK_NARROW};
+  if (dt == hfrep::DT_BF16 && N > 64) return {hfrep::DK_LINEAR2};
+  return {hfrep::DK_LINEAR};
+}
+// input gradient dx (M, N) = dz (M, K) W^T, W stored (N, K): K is the reduction length here too
+hfrep::DenseRoute linear_dgrad_route(int dt, int K, int N) {
+  if (hfrep::skinny_supported(N, K)) return {hfrep::DK_SKINNY};
+  if (dt == hfrep::DT_F32 && hfrep::narrowf_supported(K, N)) return hfrep::narrowf_route(K, N);
+  if (dt == hfrep::DT_F32 && hfrep::widef_supported(K, N)) return hfrep::widef_route(K, N);
+  if (dt == hfrep::DT_BF16 && N > 64) return {hfrep::DK_LINEAR2};
+  return {hfrep::DK_LINEAR};
+}
+// weight gradient gW (K, N) += x (M, K)^T dz (M, N)
+hfrep::DenseRoute linear_wgrad_route(int dt, int K, int N, int shiftT) {
+  if (shiftT == 0 && hfrep::skinny_supported(K, N)) return {hfrep::DK_SKINNY};
+  return hfrep::wgrad_route(dt, K, N, shiftT);
+}
+
+std::string dense_route_name(const hfrep::DenseRoute& r) {
+  const auto p = [](int v) { return std::to_string(v); };
+  switch (r.kernel) {
+    case hfrep::DK_SKINNY: return "skinny";
+    case hfrep::DK_NARROWF: return "narrowf<" + p(r.p0) + "," + p(r.p1) + "," + p(r.p2) + ">";
+    case hfrep::DK_WIDEF: return "widef<" + p(r.p0) + ">";
+    case hfrep::DK_NARROW: return "narrow";
+    case hfrep::DK_LINEAR2: return "linear2";
+    case hfrep::DK_LINEAR: return "linear";
+    case hfrep::DK_WGRAD_NARROW: return "wgrad_narrow";
+    case hfrep::DK_WGRAD_F32S: return "wgrad_f32s<" + p(r.p0) + "," + p(r.p1) + ">";
+    case hfrep::DK_WGRAD: return "wgrad";
+    case hfrep::DK_HEAD_CS: return "head_cs<" + p(r.p0) + ">";
+  }
+  TORCH_CHECK(false, "dense_route: unknown kernel ", r.kernel);
+}
+
+// op: "linear" (x (M, K), W (K, N)), "linear_dgrad" (dz (M, K), W (N, K)), "linear_wgrad_" (x (M, K), dz (M, N))
+// or "linear_head_cs" (x (M, K), N = 1); M does not enter any route today
+std::string dense_route(std::string op, bool bf16, int64_t M, int64_t K, int64_t N, int64_t shiftT) {
+  TORCH_CHECK(M >= 1 && K >= 1 && N >= 1 && shiftT >= 0, "dense_route: M, K, N >= 1 and shiftT >= 0");
+  const int dt = bf16 ? hfrep::DT_BF16 : hfrep::DT_F32;
+  if (op == "linear") return dense_route_name(linear_route(dt, (int)K, (int)N));
+  if (op == "linear_dgrad") return dense_route_name(linear_dgrad_route(dt, (int)K, (int)N));
+  if (op == "linear_wgrad_") return dense_route_name(linear_wgrad_route(dt, (int)K, (int)N, (int)shiftT));
+  if (op == "linear_head_cs") {
+    TORCH_CHECK(N == 1 && hfrep::skinny_fwd_cs_supported((int)K), "dense_route: linear_head_cs needs N = 1, K % 8 == 0, K <= 4096");
+    return dense_route_name(hfrep::head_cs_route((int)K));
+  }
+  TORCH_CHECK(false, "dense_route: op must be linear, linear_dgrad, linear_wgrad_ or linear_head_cs, got ", op);
+}
+
 // out (optional): a contiguous (M, N) destination of x's dtype, e.g. a row slice of a larger buffer
 // (the generator writes its fake batch straight into the critic's [real; fake] input)
 Tensor linear(Tensor x, Tensor W, optional<Tensor> b, int64_t act, optional<Tensor> out) {
@@ -70,19 +128,20 @@ Tensor linear(Tensor x, Tensor W, optional<Tensor> b, int64_t act, optional<Tens
                     out->scalar_type() == x.scalar_type() && out->numel() == (int64_t)M * N,
                 "linear: out must be a contiguous (M, N) tensor of x's dtype on x's device");
   Tensor y = out.has_value() ? out->view({M, N}) : out_empty({M, N}, x.options());
-  if (hfrep::skinny_supported(K, N))
+  const int kernel = linear_route(dt_of(x), K, N).kernel;
+  if (kernel == hfrep::DK_SKINNY)
     hfrep::launch_skinny_fwd(dt_of(x), x.data_ptr(), W.data_ptr<float>(), b.has_value() ? b->data_ptr<float>() : nullptr,
                              y.data_ptr(), M, K, N, (int)act, cur_stream(x));
-  else if (dt_of(x) == hfrep::DT_F32 && hfrep::narrowf_supported(K, N))
+  else if (kernel == hfrep::DK_NARROWF)
     hfrep::launch_narrowf(x.data_ptr<float>(), W.data_ptr<float>(), N, 1, b.has_value() ? b->data_ptr<float>() : nullptr,
                           y.data_ptr<float>(), M, K, N, (int)act, cur_stream(x));
-  else if (dt_of(x) == hfrep::DT_F32 && hfrep::widef_supported(K, N))
+  else if (kernel == hfrep::DK_WIDEF)
     hfrep::launch_widef(x.data_ptr<float>(), W.data_ptr<float>(), N, 1, b.has_value() ? b->data_ptr<float>() : nullptr,
                         y.data_ptr<float>(), M, K, N, (int)act, cur_stream(x));
-  else if (dt_of(x) == hfrep::DT_BF16 && hfrep::narrow_supported(K, N))
+  else if (kernel == hfrep::DK_NARROW)
     hfrep::launch_narrow_fwd(x.data_ptr(), W.data_ptr<float>(), b.has_value() ? b->data_ptr<float>() : nullptr,
                              y.data_ptr(), M, K, N, (int)act, cur_stream(x));
-  else if (dt_of(x) == hfrep::DT_BF16 && N > 64)
+  else if (kernel == hfrep::DK_LINEAR2)
     hfrep::launch_linear2(x.data_ptr(), W.data_ptr<float>(), b.has_value() ? b->data_ptr<float>() : nullptr,
                           y.data_ptr(), M, N, K, 0, (int)act, cur_stream(x));
   else
@@ -124,15 +183,16 @@ Tensor linear_dgrad(Tensor dz, Tensor W) {
   const int M = dz.size(0), K = dz.size(1), N = W.size(0);
   Tensor dx = out_empty({M, N}, dz.options());
   // dx = dz . W^T : W stored (N, K) row-major -> w_trans
-  if (hfrep::skinny_supported(N, K))
+  const int kernel = linear_dgrad_route(dt_of(dz), K, N).kernel;
+  if (kernel == hfrep::DK_SKINNY)
     hfrep::launch_skinny_dgrad(dt_of(dz), dz.data_ptr(), W.data_ptr<float>(), dx.data_ptr(), M, N, K, cur_stream(dz));
-  else if (dt_of(dz) == hfrep::DT_F32 && hfrep::narrowf_supported(K, N))  // B[k][n] = W[n][k]
+  else if (kernel == hfrep::DK_NARROWF)  // B[k][n] = W[n][k]
     hfrep::launch_narrowf(dz.data_ptr<float>(), W.data_ptr<float>(), 1, K, nullptr, dx.data_ptr<float>(), M, K, N, 0,
                           cur_stream(dz));
-  else if (dt_of(dz) == hfrep::DT_F32 && hfrep::widef_supported(K, N))  // B[k][n] = W[n][k]
+  else if (kernel == hfrep::DK_WIDEF)  // B[k][n] = W[n][k]
     hfrep::launch_widef(dz.data_ptr<float>(), W.data_ptr<float>(), 1, K, nullptr, dx.data_ptr<float>(), M, K, N, 0,
                         cur_stream(dz));
-  else if (dt_of(dz) == hfrep::DT_BF16 && N > 64)
+  else if (kernel == hfrep::DK_LINEAR2)
     hfrep::launch_linear2(dz.data_ptr(), W.data_ptr<float>(), nullptr, dx.data_ptr(), M, N, K, 1, 0, cur_stream(dz));
   else
     hfrep::launch_linear(dt_of(dz), dz.data_ptr(), W.data_ptr<float>(), nullptr, dx.data_ptr(), M, N, K, 1, 0,
@@ -148,7 +208,7 @@ void linear_wgrad_(Tensor x, Tensor dz, Tensor gW, optional<Tensor> gb, int64_t 
   if (gb.has_value()) { CHECK_F32(*gb); TORCH_CHECK(gb->numel() == dz.size(1), "wgrad: gb size"); }
   GUARD(x);
   const int M = x.size(0), K = x.size(1), N = dz.size(1);
-  if (shiftT == 0 && hfrep::skinny_supported(K, N)) {
+  if (linear_wgrad_route(dt_of(x), K, N, (int)shiftT).kernel == hfrep::DK_SKINNY) {
     Tensor ws = out_empty({(int64_t)hfrep::skinny_wgrad_workspace_floats(M, K, N)}, x.options().dtype(at::kFloat));
     hfrep::launch_skinny_wgrad(dt_of(x), x.data_ptr(), dz.data_ptr(), gW.data_ptr<float>(),
                                gb.has_value() ? gb->data_ptr<float>() : nullptr, M, K, N, ws.data_ptr<float>(),
@@ -1174,6 +1234,7 @@ TORCH_LIBRARY(hfrep, m) {
   m.def("lstm_tbwd(Tensor? dH, Tensor dHd, Tensor gates, Tensor cs, Tensor zds, Tensor cds, Tensor U, int act) -> (Tensor, Tensor)");
   m.def("lstmf_supported(int H, int K, int act) -> bool", &lstmf_supported);  // no tensor inputs: catch-all kernel
   m.def("narrowf_supported(int K, int N) -> bool", &narrowf_supported);
+  m.def("dense_route(str op, bool bf16, int M, int K, int N, int shiftT) -> str", &dense_route);  // no tensor inputs: catch-all kernel
   m.def("set_lstmf_fwd_impl(int v) -> int", &set_lstmf_fwd_impl);
   m.def("set_lstmf_fwd100_impl(int v) -> int", &set_lstmf_fwd100_impl);
   m.def("set_lstmf_bwd_impl(int v) -> int", &set_lstmf_bwd_impl);

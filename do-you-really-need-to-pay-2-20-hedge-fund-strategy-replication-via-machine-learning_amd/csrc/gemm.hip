@@ -428,10 +428,17 @@ narrow_wgrad_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ D, 
   }
 }
 
+DenseRoute wgrad_route(int dt, int K, int N, int shiftT) {
+  if (dt == DT_BF16 && shiftT == 0 && K % 4 == 0 && K + 1 <= 128 && N <= 32) return {DK_WGRAD_NARROW};
+  if (dt == DT_F32 && shiftT == 0 && wgrad_f32s_ok(K, N)) return {DK_WGRAD_F32S, (K + 1 + 31) / 32, (N + 31) / 32};
+  return {DK_WGRAD};
+}
+
 void launch_wgrad(int dt, const void* X, const void* D, float* gW, float* gb, int M, int K, int N, int shiftT,
                   float* ws, hipStream_t s) {
   if (M <= 0) return;
-  if (dt == DT_BF16 && shiftT == 0 && K % 4 == 0 && K + 1 <= 128 && N <= 32) {
+  const DenseRoute route = wgrad_route(dt, K, N, shiftT);
+  if (route.kernel == DK_WGRAD_NARROW) {
     const int splits = wgrad_splits(M, K, N);
     const int rps = ((M + splits - 1) / splits + 31) / 32 * 32;
     const int z = (M + rps - 1) / rps;
@@ -441,11 +448,11 @@ void launch_wgrad(int dt, const void* X, const void* D, float* gW, float* gb, in
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, ws, gW, gb, z, K, N, gb != nullptr ? 1 : 0);
     return;
   }
-  if (dt == DT_F32 && shiftT == 0 && wgrad_f32s_ok(K, N)) {
+  if (route.kernel == DK_WGRAD_F32S) {
     const int P = wgrad_f32s_splits(M);
     const int rps = ((M + P - 1) / P + WSR - 1) / WSR * WSR;
     const int z = (M + rps - 1) / rps;
-    const int ni = (K + 1 + 31) / 32, nj = (N + 31) / 32;
+    const int ni = route.p0, nj = route.p1;
     auto go = [&](auto k) {
       hipLaunchKernelGGL(k, dim3(z), dim3(256), 0, s, (const float*)X, (const float*)D, ws, M, K, N, rps);
     };

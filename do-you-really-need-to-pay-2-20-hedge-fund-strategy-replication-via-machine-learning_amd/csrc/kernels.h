@@ -9,6 +9,30 @@ namespace hfrep {
 // storage dtype codes shared by all launchers
 enum DType : int { DT_F32 = 0, DT_BF16 = 1 };
 
+// ---- Dense routing: which kernel (and which instantiation) a Dense product runs on ----
+// The ops in bindings.cpp and the launchers below switch on these, and the tensor-free op
+// dense_route(op, bf16, M, K, N, shiftT) prints them, so a test can assert the kernel its shape ran on.
+enum DenseKernel : int {
+  DK_SKINNY,        // skinny.hip skinny_fwd / skinny_dgrad / skinny_wgrad
+  DK_NARROWF,       // narrowf_kernel<NT, NQ, RS>  (p0, p1, p2)
+  DK_WIDEF,         // widef_kernel<NQ>            (p0)
+  DK_NARROW,        // narrow_fwd_kernel (bf16)
+  DK_LINEAR2,       // linear2_kernel (bf16)
+  DK_LINEAR,        // linear_kernel<T>
+  DK_WGRAD_NARROW,  // narrow_wgrad_kernel (bf16)
+  DK_WGRAD_F32S,    // wgrad_f32s_kernel<NI, NJ>   (p0, p1)
+  DK_WGRAD,         // wgrad_kernel<T>
+  DK_HEAD_CS        // skinny_fwd_cs_kernel<T, NC> (p0)
+};
+struct DenseRoute {
+  int kernel;
+  int p0 = 0, p1 = 0, p2 = 0;  // the instantiation's template parameters (see DenseKernel)
+};
+DenseRoute narrowf_route(int K, int N);                    // skinny.hip: valid where narrowf_supported(K, N)
+DenseRoute widef_route(int K, int N);                      // skinny.hip: valid where widef_supported(K, N)
+DenseRoute head_cs_route(int K);                           // skinny.hip: valid where skinny_fwd_cs_supported(K)
+DenseRoute wgrad_route(int dt, int K, int N, int shiftT);  // gemm.hip: the kernel launch_wgrad runs
+
 // ---- lstm.hip (return false if H is not an instantiated hidden size) ----
 bool launch_lstm_fwd(int dt, const void* zx, const float* U, void* hs, void* gates, void* cs, int B, int Tn, int H,
                      int act, hipStream_t s);

@@ -546,11 +546,12 @@ __global__ void __launch_bounds__(256) widef_kernel(const float* __restrict__ x,
 }
 
 bool widef_supported(int K, int N) { return K >= 4 && K <= WF_KMAX && K % 4 == 0 && N > 4; }
+DenseRoute widef_route(int K, int) { return {DK_WIDEF, (K + 15) / 16}; }  // NQ 16-wide k groups (K <= 320: <= 20)
 
 void launch_widef(const float* x, const float* B, int sk, int sn, const float* b, float* y, int M, int K, int N,
                   int act, hipStream_t s) {
   if (M <= 0) return;
-  const int nq = (K + 15) / 16, nch = (M + 15) / 16, ncb = (N + 16 * WF_NT - 1) / (16 * WF_NT);
+  const int nq = widef_route(K, N).p0, nch = (M + 15) / 16, ncb = (N + 16 * WF_NT - 1) / (16 * WF_NT);
   const size_t smem = (size_t)16 * nq * WF_LDB * 4;
   const int grid = std::max(1, std::min((nch + 3) / 4, std::max(1, device_cu_count() / ncb)));
   // every NQ instantiation needs its own MaxDynamicSharedMemorySize attribute (NQ >= 9 is > 64 KiB of
@@ -578,13 +579,17 @@ void launch_widef(const float* x, const float* B, int sk, int sn, const float* b
 bool narrowf_supported(int K, int N) {
   return N > 4 && N <= 112 && (K == 32 || K == 36 || K == 64 || K == 100 || K == 128);
 }
+// NT 16-column output tiles (N <= 112: <= 7), NQ whole 16-wide k groups and RS 4-wide remainder k-steps
+// (K = 16 NQ + 4 RS; launch_narrowf holds the one table of instantiated (NQ, RS))
+DenseRoute narrowf_route(int K, int N) { return {DK_NARROWF, std::min((N + 15) / 16, 7), K / 16, K % 16 / 4}; }
 
 void launch_narrowf(const float* x, const float* B, int sk, int sn, const float* b, float* y, int M, int K, int N,
                     int act, hipStream_t s) {
   if (M <= 0) return;
   const int nch = (M + 15) / 16;
   const int grid = std::max(1, std::min((nch + 3) / 4, device_cu_count() * 4));
-  const int nt = (N + 15) / 16;
+  const DenseRoute route = narrowf_route(K, N);
+  const int nt = route.p0;
 #define HFREP_NARROWF(NQ, RS)                                                                                        \
   switch (nt) {                                                                                                      \
     case 1: hipLaunchKernelGGL((narrowf_kernel<1, NQ, RS>), dim3(grid), dim3(256), 0, s, x, B, sk, sn, b, y, M, N, act); break; \
@@ -595,12 +600,12 @@ void launch_narrowf(const float* x, const float* B, int sk, int sn, const float*
     case 6: hipLaunchKernelGGL((narrowf_kernel<6, NQ, RS>), dim3(grid), dim3(256), 0, s, x, B, sk, sn, b, y, M, N, act); break; \
     default: hipLaunchKernelGGL((narrowf_kernel<7, NQ, RS>), dim3(grid), dim3(256), 0, s, x, B, sk, sn, b, y, M, N, act); break; \
   }
-  switch (K) {
-    case 32: HFREP_NARROWF(2, 0) break;
-    case 36: HFREP_NARROWF(2, 1) break;
-    case 64: HFREP_NARROWF(4, 0) break;
-    case 100: HFREP_NARROWF(6, 1) break;
-    default: HFREP_NARROWF(8, 0) break;
+  switch (10 * route.p1 + route.p2) {  // (NQ, RS)
+    case 20: HFREP_NARROWF(2, 0) break;   // K = 32
+    case 21: HFREP_NARROWF(2, 1) break;   // K = 36
+    case 40: HFREP_NARROWF(4, 0) break;   // K = 64
+    case 61: HFREP_NARROWF(6, 1) break;   // K = 100
+    default: HFREP_NARROWF(8, 0) break;   // K = 128
   }
 #undef HFREP_NARROWF
 }
@@ -633,6 +638,8 @@ void launch_skinny_fwd(int dt, const void* x, const float* W, const float* b, vo
 
 // the fused head forward + signed column sum (N = 1, K % 8 == 0, K <= 4096)
 bool skinny_fwd_cs_supported(int K) { return K > 0 && K % 8 == 0 && K <= 4096; }
+// NC column chunks of 8 per lane: 5 covers K / 8 <= 320 (K <= 2560), 8 the rest (K / 8 <= 512)
+DenseRoute head_cs_route(int K) { return {DK_HEAD_CS, K / 8 <= 320 ? 5 : 8}; }
 static int skinny_cs_grid(int M) {
   const int64_t groups = ((int64_t)M + 4 * SK_ROWS - 1) / (4 * SK_ROWS);
   return (int)std::max<int64_t>(1, std::min<int64_t>(groups, (int64_t)device_cu_count() * 2));
@@ -648,12 +655,12 @@ void launch_skinny_fwd_cs(int dt, const void* x, const float* W, const float* b,
   auto go = [&](auto kern, auto* xp, auto* yp) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), sm, s, xp, W, b, yp, M, K, split, wa, wb, ws);
   };
-  const int kc = K / 8;
+  const int nc = head_cs_route(K).p0;
   if (dt == DT_BF16) {
-    if (kc <= 320) go(skinny_fwd_cs_kernel<bf16_t, 5>, (const bf16_t*)x, (bf16_t*)y);
+    if (nc == 5) go(skinny_fwd_cs_kernel<bf16_t, 5>, (const bf16_t*)x, (bf16_t*)y);
     else go(skinny_fwd_cs_kernel<bf16_t, 8>, (const bf16_t*)x, (bf16_t*)y);
   } else {
-    if (kc <= 320) go(skinny_fwd_cs_kernel<float, 5>, (const float*)x, (float*)y);
+    if (nc == 5) go(skinny_fwd_cs_kernel<float, 5>, (const float*)x, (float*)y);
     else go(skinny_fwd_cs_kernel<float, 8>, (const float*)x, (float*)y);
   }
   const int total = K + 1;
